@@ -5,10 +5,17 @@ the Wan-2.1 1.3B StableAvatar model + the 3-D causal VAE decode to 81 frames.
 One bench "step" = one whole clip (50 DiT forwards at B=3, L=21504 + 50 fused CFG/Euler steps +
 VAE decode), inputs resident in HBM.  `python bench.py --gpus N --steps K --warmup W`.
 
+A plain run does what the headline figure needs and no more: set-up, W warmup clips, the K timed clips, the
+outputs of the last timed clip as .npy files if `--dump-outputs DIR` is given, and the JSON line.  `--full` adds
+everything else the benchmark measures, each outside the timed region: the CPU baseline (a child process), the
+per-kernel-class times of the last warmup clip, the SCLK samples, the VAE encode, `--dit14`, and at N > 1 the
+sequence-parallel self-check and the `replicas` measurement.  The JSON keys are the same in both; what a plain
+run leaves out is null.
+
 N = 1: one clip on one GPU.  N > 1 (one process per GPU; torch.distributed.run sets RANK/WORLD_SIZE,
 and without it this script starts that launcher itself before touching the GPU):
   --mode sp (default)   ONE clip, Ulysses sequence parallel over all ranks on RCCL (BASELINE config 3,
-                        strong scaling); the JSON also carries `replicas` = one clip per rank timed in
+                        strong scaling); with --full the JSON also carries `replicas` = one clip per rank timed in
                         the same processes (--replica-steps, 0 to skip)
   --mode replicas       one clip per rank, no data-path collective (weak scaling)
   --mode window-dp      one long clip (--video-frames) with its sliding windows spread over the ranks
@@ -48,6 +55,13 @@ def parse(argv=None):
     p.add_argument("--size", type=int, default=512)
     p.add_argument("--sample-steps", type=int, default=50)
     p.add_argument("--overlap", type=int, default=15)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the per-kernel-class "
+                        "times, the SCLK samples, the VAE encode, --dit14, and at N>1 the SP self-check and the "
+                        "replicas measurement (the --no-* options below select among these)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step returned to DIR/<name>.npy (float32; "
+                        "outputs above 8 Mi elements as a fixed, seeded sample of their elements)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-cpu-config1", action="store_true",
                    help="skip the config-1 run of the CPU oracle inside cpu_baseline")
@@ -411,6 +425,7 @@ class ClipWorkload:
         lat = self.pipe.denoise(self.latents, self.y, self.ctx, self.clip, self.feats, self.sched.timesteps,
                                 self.sched.sigmas, clip_length=a.frames, seq_len=self.seq_len, overlap=a.overlap,
                                 text_guide_scale=3.0, audio_guide_scale=5.0)
+        self.last_latents = lat  # the decode's input, kept for --dump-outputs
         return self.vae.decode_clip(lat[0].float(), post=True)
 
     def check(self, video):
@@ -567,14 +582,15 @@ class ClockSampler:
                 "samples": len(s), "period_s": self.period, "source": f"amdsmi {self.field}"}
 
 
-def timed(work, steps, warmup, world, dev, events=False, before_timed=None):
+def timed(work, steps, warmup, world, dev, events=False, before_timed=None, extras=False):
     """W untimed warmup steps, then EXACTLY K steps between barriers; the max over ranks.
     before_timed(warmup_seconds) runs after the warmup, before the opening barrier.  events=True: the
-    self-attention events (roofline) and the SCLK samples of the timed clips are recorded, and the per-kernel-class
+    self-attention events of the timed clips are recorded (roofline; they are part of the timed path and take
+    no run of their own).  extras=True (--full) adds the SCLK samples of the timed clips and the per-kernel-class
     HIP events (ktimer: one event after every library launch) on the LAST WARMUP clip, so that the timed region
     carries no per-launch event but the self-attention's (work.kernels)."""
     kt = clk = None
-    if events:
+    if events and extras:
         from stableavatar_amd.ktimer import KernelTimer
         kt = KernelTimer() if dev.type == "cuda" and os.environ.get("SA_BENCH_KTIMER", "1") != "0" else None
         clk = ClockSampler(dev) if dev.type == "cuda" and int(os.environ.get("RANK", "0")) == 0 else None
@@ -609,7 +625,7 @@ def timed(work, steps, warmup, world, dev, events=False, before_timed=None):
         barrier(world, dev)
         dt = time.perf_counter() - t0
         progress(f"timed {steps} steps {dt:.1f}s")
-        if events:
+        if events and extras:
             rec = kt.summary(1) if (kt is not None and kt_ms is not None) else {}
             if rec:
                 rec["frac_of_clip_ms"] = round(rec["sum_ms_per_clip"] / kt_ms, 4)
@@ -659,6 +675,30 @@ def attn_traffic(seq_len, layout):
     return tj["hbm_bytes_per_launch"], f"profiles/pmc_attn_traffic.json ({tj.get('source', 'rocprofv3 --pmc')})"
 
 
+DUMP_MAX_ELEMS = 8 * 2 ** 20  # per array: 32 MiB of float32, so the video + the latents stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float32.  An array above DUMP_MAX_ELEMS elements is
+    written as a sample of its flattened elements at DUMP_MAX_ELEMS sorted indices drawn by a generator seeded
+    with the array's element count alone, so two builds run with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(n)
+            idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+            a = flat[idx.to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = {"shape": list(t.shape), "saved": list(a.shape), "sampled": n > DUMP_MAX_ELEMS}
+    return written
+
+
 POST_RESERVE_S = 6.0  # after the timed region: result assembly, JSON, process-group teardown (~1 s measured, r03)
 
 
@@ -683,8 +723,16 @@ def run(args, world, rank, dev, work_factory=ClipWorkload, cpu=None):
             deadline = budget_end - args.steps * per_step - POST_RESERVE_S
         cpu.wait(deadline, required_by=time.time() + 180.0)
 
-    dt, video = timed(work, args.steps, args.warmup, world, dev, events=True, before_timed=collect_cpu)
+    dt, video = timed(work, args.steps, args.warmup, world, dev, events=True, before_timed=collect_cpu,
+                      extras=args.full)
     work.check(video)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"video": video}
+        if getattr(work, "last_latents", None) is not None:
+            arrays["latents"] = work.last_latents
+        dumped = dump_outputs(args.dump_outputs, arrays)
+        progress(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     attn_ms, attn_share = work.attention_launch_ms()
     seq_len = work.seq_len
     attn_flop = flops.self_attention_flops(B=3, L=seq_len) * attn_share
@@ -700,11 +748,11 @@ def run(args, world, rank, dev, work_factory=ClipWorkload, cpu=None):
     path_flop = n_fwd * flops.dit_forward_flops(B=3, L=seq_len, n_frames=work.fpb) + \
         flops.vae_decode_flops(work.T, work.h, work.h)
     sp_check = None
-    if layout == "sp" and world > 1 and hasattr(work, "sp_check"):
+    if args.full and layout == "sp" and world > 1 and hasattr(work, "sp_check"):
         sp_check = work.sp_check()
         progress(f"sp check: {sp_check}")
     replicas = None
-    if layout == "sp" and args.replica_steps > 0:
+    if args.full and layout == "sp" and args.replica_steps > 0:
         # the layout switch changes the DiT's per-rank token count (workspaces, segment tables): untimed
         # warmup clips first
         est = (dt / args.steps) * world * (args.replica_steps + args.replica_warmup)
@@ -720,13 +768,13 @@ def run(args, world, rank, dev, work_factory=ClipWorkload, cpu=None):
         else:
             skipped.append("replicas (would not fit the time budget)")
     enc = None
-    if not args.no_encode and rank == 0 and hasattr(work, "vae"):
+    if args.full and not args.no_encode and rank == 0 and hasattr(work, "vae"):
         if time.time() + 10.0 < budget_end:
             enc = vae_encode_ms(work.vae, args.frames, args.size, dev)
         else:
             skipped.append("vae_encode (time budget)")
     dit14 = None
-    if world == 1 and args.dit14 and hasattr(work, "dit"):
+    if args.full and world == 1 and args.dit14 and hasattr(work, "dit"):
         if time.time() + 40.0 < budget_end:
             from stableavatar_amd.kbench import bench_dit14
             dit14 = dict(bench_dit14(), note="BASELINE config 4's model (Wan-14B StableAvatar widths: dim 5120, 40 "
@@ -771,8 +819,11 @@ def run(args, world, rank, dev, work_factory=ClipWorkload, cpu=None):
                         "launch_ms": round(attn_ms, 3) if attn_ms else None, "flop_per_launch": attn_flop},
            "path_mfma_frac": round(path_flop * args.steps / dt / PEAK_BF16 / (world if shared else 1), 4),
            "cpu_baseline": cpu_res, "vae_encode": enc, "config_4_dit14": dit14,
+           "full": bool(args.full),
            "time_budget": {"budget_s": args.time_budget, "elapsed_s": round(time.time() - T0, 1),
                            "skipped": skipped}}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if replicas is not None:
         out["replicas"] = replicas
     if sp_check is not None:
@@ -801,7 +852,7 @@ def main(argv=None, work_factory=ClipWorkload, device=None):
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = CpuBaseline(args)  # started before this process touches the GPU (a plain child, no exec of ours)
     try:
         if device is None:

@@ -91,7 +91,8 @@ def _run(world, argv, tmp_path):
 
 
 def test_bench_sp_default_world2(tmp_path):
-    j = _run(2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-encode"], tmp_path)
+    j = _run(2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-encode"],
+             tmp_path)
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["warmup"] == 1
     assert j["scaling"] == "strong" and j["config"]["parallelism"] == "ulysses2"
     assert j["config"]["global_batch"] == 3
@@ -128,7 +129,7 @@ def test_bench_cpu_baseline_child_world1(capsys):
     """N = 1: the CPU baseline runs in a child process started before the GPU work, is collected after the
     warmup (never inside the timed region) and lands in the JSON with the thread count it used; the
     JSON records the time budget."""
-    rc = bench.main(["--steps", "1", "--warmup", "1", "--size", "64", "--frames", "17", "--no-cpu-config1",
+    rc = bench.main(["--steps", "1", "--warmup", "1", "--size", "64", "--frames", "17", "--full", "--no-cpu-config1",
                      "--no-encode"], work_factory=FakeClip, device="cpu")
     assert rc == 0
     j = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
@@ -137,6 +138,71 @@ def test_bench_cpu_baseline_child_world1(capsys):
     assert "1 of 30 DiT blocks at B=3,L=80" in c["sample"]
     assert c["config_1"]["value"] is None and c["config_1"]["skipped"] == "not run"
     assert j["time_budget"]["budget_s"] == 540.0 and j["time_budget"]["elapsed_s"] > 0
+
+
+def _plain(argv, capsys, monkeypatch):
+    """a plain N = 1 run on the stand-in workload; any child process it starts fails the test"""
+    made = []
+
+    def factory(*a):
+        made.append(FakeClip(*a))
+        return made[-1]
+
+    def no_child(*a, **k):
+        raise AssertionError("a plain run starts no child process")
+
+    monkeypatch.setattr(bench.subprocess, "Popen", no_child)
+    assert bench.main(argv, work_factory=factory, device="cpu") == 0
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1, "one JSON line on stdout"
+    return json.loads(lines[0]), made[0]
+
+
+def test_bench_plain_run_is_lean(capsys, monkeypatch):
+    """Without --full: warmup + exactly --steps timed steps and the result line; no CPU baseline child, no
+    per-kernel record, no VAE encode.  The keys of the result line stay, what was not measured is null."""
+    j, work = _plain(["--gpus", "1", "--steps", "3", "--warmup", "2", "--size", "64", "--frames", "17"], capsys,
+                     monkeypatch)
+    assert work.steps_run == 5 and j["steps"] == 3 and j["warmup"] == 2
+    assert j["full"] is False and j["cpu_baseline"] is None and j["vae_encode"] is None
+    assert j["config_4_dit14"] is None and "kernels" not in j and "replicas" not in j
+    assert j["metric"] == bench.METRIC and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "bf16" and j["value"] > 0 and j["ms_per_step"] >= 0
+    assert j["roofline"]["launch_ms"] == 2.0  # the self-attention events of the timed steps: part of the timed path
+    assert len(work.events or []) == 0 and j["time_budget"]["skipped"] == []
+
+
+def test_bench_dump_outputs(tmp_path, capsys, monkeypatch):
+    """--dump-outputs writes what the last timed step returned as float32 .npy; an output above the size cap is
+    a fixed sample of its elements, the same from run to run."""
+    import numpy as np
+
+    class Ramp(FakeClip):
+        def step(self):
+            super().step()
+            self.last_latents = torch.full((1, 2, 3), float(self.steps_run)).bfloat16()
+            return torch.arange(3 * self.out_frames * 64, dtype=torch.float64).reshape(3, self.out_frames, 8, 8) \
+                + self.steps_run
+
+    d = tmp_path / "out"
+    argv = ["--steps", "2", "--warmup", "1", "--size", "64", "--frames", "17", "--dump-outputs", str(d)]
+    monkeypatch.setattr(bench.subprocess, "Popen", None)
+    assert bench.main(argv, work_factory=Ramp, device="cpu") == 0
+    j = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    v, lat = np.load(d / "video.npy"), np.load(d / "latents.npy")
+    assert v.dtype == np.float32 and v.shape == (3, 17, 8, 8) and lat.dtype == np.float32
+    assert v.flat[0] == 3.0 and v.flat[-1] == 3 * 17 * 64 - 1 + 3.0 and (lat == 3.0).all()  # the LAST timed step
+    assert j["dumped_outputs"]["arrays"]["video"] == {"shape": [3, 17, 8, 8], "saved": [3, 17, 8, 8],
+                                                     "sampled": False}
+    # above the cap: a seeded sample of the flattened elements, identical from call to call
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    r1 = bench.dump_outputs(str(tmp_path / "a"), {"x": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"x": big + 0.5})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert r1["x"] == {"shape": [50, 100], "saved": [100], "sampled": True}
+    assert a.shape == (100,) and a.dtype == np.float32 and (np.diff(a) >= 0).all() and len(set(a.tolist())) > 50
+    assert (b - a == 0.5).all(), "the same elements are sampled in both calls"
 
 
 def test_bench_cpu_baseline_deadline(tmp_path):
