@@ -27,10 +27,12 @@ enum {
   SA_EPI_SILU_F32 = 5,      /* C(f32)  = silu(A·W^T + bias)                              */
   SA_EPI_BF16_T = 6,        /* C^T(bf16): C[n * ldc + m] = A·W^T + bias (persistent kernel, K % 128 == 0,
                                M % 4 == 0, ldc >= M): the V^T operand of sa_attn_fwd_ex kernel 4 */
-  SA_EPI_BF16_TP32 = 7      /* SA_EPI_BF16_T with row 32c + 4q + r at column 32c + 8(q & 3) + 4(q >> 2) + r
+  SA_EPI_BF16_TP32 = 7,     /* SA_EPI_BF16_T with row 32c + 4q + r at column 32c + 8(q & 3) + 4(q >> 2) + r
                                (ldc >= M rounded up to 32, ldc and strideC % 8 == 0, C 16-B aligned:
                                16-byte stores): the V^T of sa_attn_fwd_ex kernel 3, the
                                DiT's self-attention (wan_fantasy_transformer3d_1B.py:376-379 v projection) */
+  SA_EPI_GELU_TANH_MXFP8 = 8 /* sa_gemm_mxfp8 only: C(MXFP8) = SA_EPI_GELU_TANH_BF16 followed by sa_mxfp8_quant
+                               (N % 32 == 0) */
 };
 
 /* nn.Linear on bf16 activations (every Linear of wan/models/wan_fantasy_transformer3d_1B.py
@@ -137,6 +139,38 @@ int sa_layernorm_mod(const void* x, int64_t ldx, int in_dtype, void* out, int64_
                      const float* weight, const float* bias, const float* shift, const float* scale,
                      int64_t mod_bstride, const float* gate, int rows_per_batch, int M, int C, float eps,
                      void* stream);
+
+/* ---- MXFP8 (opt-in fp8 FFN mode; no counterpart in the reference, which computes every Linear in bf16) ----
+ * Format: blocks of 32 consecutive K elements; elements OCP e4m3fn, one byte each, uint8 [rows][ld], K-contiguous;
+ * one E8M0 scale byte s per block, uint8 [rows][lds], byte k / 32 of a row; value = 2^(s - 127) * element.
+ * Quantising a block with absolute maximum amax: e = the smallest integer with amax * 2^-e <= 448 (0 for an all-zero
+ * block), s = clamp(e + 127, 0, 254), element = RNE(x * 2^-e).  NaN / Inf inputs are out of contract.
+ * stableavatar_amd/mxfp8.py (quantize / dequantize) is the definition; the kernels match it bit for bit. */
+
+/* bf16 x [M][ldx] (K columns) -> q, scales.  K % 32 == 0, ldx / ldq % 8 == 0, x 16-B and q 8-B aligned.
+ * Quantises the FFN weights at pack time and is the second half of the fused forms below. */
+int sa_mxfp8_quant(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K,
+                   void* stream);
+
+/* sa_layernorm_mod (fp32 or bf16 in; affine, AdaLN modulate; no gated residual) with MXFP8 output: bit-identical to
+ * sa_layernorm_mod with bf16 output followed by sa_mxfp8_quant.  The norm2 + modulate in front of the FFN
+ * (wan_fantasy_transformer3d_1B.py:687) when the fp8 FFN mode is on.  C % 32 == 0, ldo % 8 == 0, out 8-B aligned. */
+int sa_layernorm_mod_mxfp8(const void* x, int64_t ldx, int in_dtype, void* out, int64_t ldo, void* out_scales,
+                           int64_t lds, const float* weight, const float* bias, const float* shift, const float* scale,
+                           int64_t mod_bstride, int rows_per_batch, int M, int C, float eps, void* stream);
+
+/* nn.Linear on MXFP8 operands (the DiT's ffn.0 / ffn.2, wan_fantasy_transformer3d_1B.py:644-646, :687-691, when the
+ * fp8 FFN mode is on): C[M,N] = epi(deq(A)[M,K] · deq(W)[N,K]^T + bias), fp32 accumulation on
+ * v_mfma_scale_f32_16x16x128_f8f6f4.  K % 128 == 0, lda/ldw % 16 == 0, A/W 16-B aligned; scale rows are read a
+ * dword at a time: ldas/ldws % 4 == 0, 4-B aligned; ldc % 4 == 0, C (and residual, gate) 16-B aligned.
+ * epilogue: SA_EPI_BF16, SA_EPI_GELU_TANH_BF16, SA_EPI_F32, SA_EPI_RES_F32 as sa_gemm_bf16 (the bf16 rounding of the
+ * Linear output before GELU / the gated residual, gate[row / rows_per_batch], residual may alias C), or
+ * SA_EPI_GELU_TANH_MXFP8 (C = element bytes, ldc in bytes, C_scales [M][ldcs]; N % 32 == 0); any other code is
+ * rejected.  C_scales is unused (may be NULL) for the other epilogues. */
+int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                  const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc, void* C_scales,
+                  int64_t ldcs, int M, int N, int K, int epilogue, const float* residual, int64_t ldr,
+                  const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream);
 
 /* WanRMSNorm over the full width on q (and k) + rope_apply (1B:295-342, :395-396, :403-404) in place.
  * rope = fp32 [1024][head_dim/2][2] (cos, sin) table or NULL (no rotation); token index

@@ -24,6 +24,9 @@ SIGNATURES = {
     "sa_attn_fwd_map": "pppppiiiillllfiipp",
     "sa_attn_fwd_split": "pppppiiiillllfipiplp",
     "sa_layernorm_mod": "pliplipppplpiiifp",
+    "sa_mxfp8_quant": "plplpliip",
+    "sa_layernorm_mod_mxfp8": "pliplplppppliiifp",
+    "sa_gemm_mxfp8": "plplplplpplpliiiiplplip",
     "sa_qk_rmsnorm_rope": "pliippiiifpiiiiiiip",
     "sa_qkv_pack": "plppiiifpiiiiiiipiiiip",
     "sa_patch_im2col": "plllipllliiiiipiip",

@@ -1,0 +1,384 @@
+// MXFP8 "NT" GEMM for the DiT's FFN Linears (opt-in fp8 FFN mode; the default path stays on gemm.hip):
+//   C[M,N] = epi(deq(A)[M,K] · deq(W)[N,K]^T + bias)
+// A and W are e4m3fn bytes, K-contiguous, with one E8M0 scale byte per 32 consecutive K elements
+// (stableavatar_amd/mxfp8.py is the definition); accumulation is fp32 on
+// v_mfma_scale_f32_16x16x128_f8f6f4.  Replaces, when the mode is on, the aten::addmm of the FFN
+// (wan_fantasy_transformer3d_1B.py:644-646 through :687-691), which has no fp8 counterpart in the reference.
+//
+// gemm_mx_kernel: 4 waves, one per SIMD, over a 256x256 tile (2 x 2 waves of 128 x 128, the 256 accumulators in
+// AGPRs, as gemm.hip's persistent kernel), K-tiles of 128 bytes staged by global_load ... lds into the bf16 kernels'
+// XOR-swizzled LDS image (a 128-element fp8 K-tile is the same 128 bytes per row as their 64 bf16), two 64-KB stages
+// (+ 2 KB of scale bytes each), one barrier per K step: tile t+1 lands while tile t multiplies.
+// Lane map of the scaled MFMA (established with the exact-integer test): lane l = (row r = l % 16, group g = l / 16)
+// supplies K bytes 16 g .. 16 g + 15 in its first four operand VGPRs and 64 + 16 g .. 64 + 16 g + 15 in the last
+// four (the 16-byte chunks g and 4 + g of the row -- the bf16 kernels' fragment addresses), and byte 0 of its scale
+// operand is the E8M0 scale of K block g (bytes 32 g .. 32 g + 31) of row r.  Operands are swapped (C^T = W·A^T) so
+// each lane holds 4 consecutive output columns of one row.
+// Also here: sa_mxfp8_quant, the bf16 -> MXFP8 quantiser (weights at pack time; the definition's GPU twin).
+#include <utility>
+
+#include "mxfp8.h"
+
+namespace {
+
+enum { EPI_BF16 = 0, EPI_GELU_BF16 = 1, EPI_F32 = 2, EPI_RES_F32 = 3, EPI_GELU_MXFP8 = 8 };
+
+typedef int __attribute__((ext_vector_type(8))) i32x8;
+
+struct MxArgs {
+  const uint8_t* A; long lda; const uint8_t* SA; long ldsa;
+  const uint8_t* W; long ldw; const uint8_t* SW; long ldsw;
+  const float* bias;
+  void* C; long ldc; uint8_t* SC; long ldsc;  // SC: the output's scale bytes (EPI_GELU_MXFP8)
+  const float* R; long ldr;                   // residual (EPI_RES_F32); may alias C
+  const float* gate; long gate_bstride;       // gate[(m / rows_per_batch) * gate_bstride + n]
+  int rows_per_batch;
+  int M, N, K;
+  int group_m;
+};
+
+constexpr int BM = 256, BN = 256, BKB = 128;  // BKB: K-tile bytes = fp8 elements
+constexpr int HALF_BYTES = 128 * BKB;         // 16 KB: 128 rows
+constexpr int STAGE_BYTES = 4 * HALF_BYTES;   // 64 KB: A0 A1 W0 W1
+constexpr int LDS_BYTES = 2 * STAGE_BYTES;    // 128 KB
+constexpr int SCALE_STAGE = 2 * 256 * 4;      // 2 KB: a K-tile's scale dwords, A rows then W rows
+constexpr int LDS_TOTAL = LDS_BYTES + 2 * SCALE_STAGE;
+
+// byte offset of 16-byte chunk c of row r in a [rows][128 B] tile (gemm.hip's swz128)
+__device__ __forceinline__ int swz128(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
+
+// gemm.hip's tile raster: runs of gm tile rows, column-major inside a run
+__device__ __forceinline__ void tile_coords(int wg, int nm, int nn, int gm, int& mt, int& nt) {
+  const int per = gm * nn;
+  const int first = (wg / per) * gm;
+  const int gsz = min(nm - first, gm);
+  const int r = wg % per;
+  mt = first + r % gsz;
+  nt = r / gsz;
+}
+
+// compile-time loop: f(std::integral_constant<int, 0>) ... f(<N - 1>)
+template <class F, int... I>
+__device__ __forceinline__ void unroll_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void unroll(F&& f) { unroll_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// LDS reads and MFMAs as inline asm, as gemm.hip's persistent kernel (cdna_hip_programming.md 5.7): hipcc keeps them
+// in program order, the accumulators stay in AGPRs ("+a") and the fragment waits are explicit
+template <int OFF>
+__device__ __forceinline__ void mx_ds(u32x4& d, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
+}
+template <int OFF>
+__device__ __forceinline__ void mx_ds32(uint32_t& d, uint32_t addr) {
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
+}
+__device__ __forceinline__ i32x8 mx_join(const u32x4& lo, const u32x4& hi) {
+  return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+// c += w (rows of W, scale byte sw) x x (rows of A, scale byte sa): e4m3 operands, scale byte 0 of each VGPR
+__device__ __forceinline__ void mx_mma(f32x4& c, const i32x8& w, const i32x8& x, int sw, int sa) {
+  asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
+               : "+a"(c)
+               : "v"(w), "v"(x), "v"(sw), "v"(sa));
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fc = lane >> 4;
+  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
+  const int wg = xcd_remap(blockIdx.x, nm * nn);
+  int mt, nt;
+  tile_coords(wg, nm, nn, g.group_m, mt, nt);
+  const int m0 = mt * BM, n0 = nt * BN;
+  const int nk = g.K / BKB;
+
+  // staging: half-tile h (0, 1 = A rows 0-127 / 128-255, 2, 3 = W) is 16 pieces of 1 KB (8 rows), four per wave;
+  // lane l of a piece writes LDS bytes 16 l.. and so reads row l / 8, chunk (l % 8) ^ swizzle.  Rows past M / N
+  // are clamped to the last row (read again, never stored), so every load stays inside the operand.
+  int goff[4][4];
+#pragma unroll
+  for (int h = 0; h < 4; ++h)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = (i * 4 + wave) * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      if (h < 2)
+        goff[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
+      else
+        goff[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
+    }
+  auto issue = [&](int kt) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + goff[h][i] + (long)kt * BKB),
+                                         LDS_PTR(smem + (kt & 1) * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024),
+                                         16, 0, 0);
+  };
+  // the K-tile's scale bytes ride along: one dword (the tile's four K blocks) per row, thread i fetching row i of
+  // the A and of the W tile into [256] dwords each behind the ring
+  const int soff_a = min(m0 + tid, g.M - 1) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+  auto issue_scales = [&](int kt) {
+    char* dst = smem + LDS_BYTES + (kt & 1) * SCALE_STAGE + wave * 256;
+    __builtin_amdgcn_global_load_lds((const void*)(g.SA + soff_a + kt * 4), LDS_PTR(dst), 4, 0, 0);
+    __builtin_amdgcn_global_load_lds((const void*)(g.SW + soff_w + kt * 4), LDS_PTR(dst + 1024), 4, 0, 0);
+  };
+
+  // per-lane fragment read bases: row m * 16 + fr of a half-tile, chunks fc and 4 + fc (swz128: the XOR term
+  // depends on fr only, so m is an immediate offset); the row's scale dword, byte fc of it shifted down to byte 0
+  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
+  const uint32_t swz = (fr >> 1) & 7;
+  const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
+  const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
+  const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
+  const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
+  const int sh = 8 * fc;
+  f32x4 acc[8][8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  issue(0);
+  issue_scales(0);
+  for (int t = 0; t < nk; ++t) {
+    // tile t has landed (every wave waits for its own pieces, then the barrier), and every wave is done reading
+    // the other stage (tile t - 1), which tile t + 1 now overwrites
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 1 < nk) {
+      issue(t + 1);
+      issue_scales(t + 1);
+    }
+    // the W fragments, every scale and A row 0 first; then row m's 8 MFMAs run while row m + 1 is read
+    const uint32_t so = (t & 1) * STAGE_BYTES, ss = (t & 1) * SCALE_STAGE;
+    u32x4 bl[8], bh[8], al[2], ah[2];
+    uint32_t sar[8], swr[8];
+    unroll<8>([&](auto n) {
+      mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
+      mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
+      mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
+      mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
+    });
+    mx_ds<0>(al[0], a_lo + so);
+    mx_ds<0>(ah[0], a_hi + so);
+    // the wait "writes" every register the reads above fill, so nothing that uses them moves above it
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
+                   "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
+                   "+v"(al[0]), "+v"(ah[0])::"memory");
+    asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
+                      "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
+                      "+v"(swr[6]), "+v"(swr[7]));
+    i32x8 b[8];
+    int sa[8], sw[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+      b[n] = mx_join(bl[n], bh[n]);
+      sa[n] = (int)(sar[n] >> sh);
+      sw[n] = (int)(swr[n] >> sh);
+    }
+    unroll<8>([&](auto mc) {
+      constexpr int m = mc.value;
+      if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
+      if constexpr (m < 7) {
+        mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
+        mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
+      }
+      const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
+#pragma unroll
+      for (int n = 0; n < 8; ++n) mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
+    });
+  }
+
+  // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
+  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+
+  // epilogue straight from the accumulators: acc[m][n] of lane (fr, fc) = row m0 + wm*128 + m*16 + fr, columns
+  // n0 + wn*128 + n*16 + 4 fc + 0..3.  Walked in column pairs (n = 2p, 2p + 1): the 32 columns of pair p in one row
+  // are one MXFP8 block, held by the four lanes fr, fr + 16, fr + 32, fr + 48.
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int cb = n0 + wn * 128 + p * 32;  // the block's first column (wave-uniform)
+    if (cb >= g.N) continue;
+    const int c[2] = {cb + 4 * fc, cb + 16 + 4 * fc};
+    float bv[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bv[h][e] = (g.bias && c[h] + e < g.N) ? g.bias[c[h] + e] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int row = m0 + wm * 128 + m * 16 + fr;
+      const bool live = row < g.M;
+      float v[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[4 * h + e] = acc[m][2 * p + h][e] + bv[h][e];
+      if constexpr (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MXFP8) {
+        // as gemm.hip's epi_row: the bf16 rounding of the Linear output, then the packed GELU
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+          const bf16x2 hb = __builtin_convertvector((f32x2){v[j], v[j + 1]}, bf16x2);
+          const f32x2 y = gelu_tanh2(__builtin_convertvector(hb, f32x2));
+          v[j] = y[0];
+          v[j + 1] = y[1];
+        }
+      }
+      if constexpr (EPI == EPI_GELU_MXFP8) {
+        // the bf16-rounded GELU output quantised: SA_EPI_GELU_TANH_BF16 followed by sa_mxfp8_quant, N % 32 == 0
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(v[j]));
+        float amax = mx_amax8(v);
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        uint32_t s;
+        const u32x2 q = mx_quant8(v, amax, &s);
+        if (live) {
+          uint8_t* C = (uint8_t*)g.C + (long)row * g.ldc;
+          *(uint32_t*)(C + c[0]) = q[0];
+          *(uint32_t*)(C + c[1]) = q[1];
+          if (fc == 0) g.SC[(long)row * g.ldsc + cb / 32] = (uint8_t)s;
+        }
+      } else if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_BF16) {
+        if (live) {
+          bf16* C = (bf16*)g.C + (long)row * g.ldc;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (c[h] + 4 <= g.N) {
+              *(bf16x4*)(C + c[h]) = (bf16x4){f2bf(v[4 * h]), f2bf(v[4 * h + 1]), f2bf(v[4 * h + 2]), f2bf(v[4 * h + 3])};
+            } else {
+              for (int e = 0; e < 4; ++e)
+                if (c[h] + e < g.N) C[c[h] + e] = f2bf(v[4 * h + e]);
+            }
+          }
+        }
+      } else {
+        if (live) {
+          float* C = (float*)g.C + (long)row * g.ldc;
+          const float* R = EPI == EPI_RES_F32 ? g.R + (long)row * g.ldr : nullptr;
+          const float* gt =
+              (EPI == EPI_RES_F32 && g.gate) ? g.gate + (long)(row / g.rows_per_batch) * g.gate_bstride : nullptr;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (c[h] + 4 <= g.N) {
+              f32x4 o = {v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
+              if constexpr (EPI == EPI_RES_F32) {
+                // the reference's nn.Linear returns bf16 under autocast; the gated residual consumes that value
+                const f32x4 r = *(const f32x4*)(R + c[h]);
+                const f32x4 gg = gt ? *(const f32x4*)(gt + c[h]) : (f32x4){1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = r[e] + bf2f(f2bf(o[e])) * gg[e];
+              }
+              *(f32x4*)(C + c[h]) = o;
+            } else {
+              for (int e = 0; e < 4; ++e)
+                if (c[h] + e < g.N) {
+                  float o = v[4 * h + e];
+                  if constexpr (EPI == EPI_RES_F32) o = R[c[h] + e] + bf2f(f2bf(o)) * (gt ? gt[c[h] + e] : 1.0f);
+                  C[c[h] + e] = o;
+                }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int EPI>
+int launch(const MxArgs& g, hipStream_t st) {
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    return true;
+  }();
+  (void)attr;
+  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
+  hipLaunchKernelGGL((gemm_mx_kernel<EPI>), dim3(nm * nn), dim3(256), LDS_TOTAL, st, g);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+struct QuantArgs {
+  const bf16* x; long ldx;
+  uint8_t* q; long ldq;
+  uint8_t* s; long lds;
+  int M, K;
+};
+
+// one wave per row, 8 elements per lane per 512-column chunk: a block is four adjacent lanes
+__global__ __launch_bounds__(256) void mxfp8_quant_kernel(QuantArgs a) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= a.M) return;
+  const bf16* x = a.x + (long)row * a.ldx;
+  for (int c0 = lane * 8; c0 < a.K; c0 += 512) {  // K % 32 == 0: the four lanes of a block leave together
+    const bf16x8 xv = *(const bf16x8*)(x + c0);
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bf2f(xv[j]);
+    float amax = mx_amax8(v);
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    uint32_t s;
+    const u32x2 q = mx_quant8(v, amax, &s);
+    *(u32x2*)(a.q + (long)row * a.ldq + c0) = q;
+    if ((lane & 3) == 0) a.s[(long)row * a.lds + c0 / 32] = (uint8_t)s;
+  }
+}
+
+}  // namespace
+
+extern "C" int sa_mxfp8_quant(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K,
+                              void* stream) {
+  if (!x || !q || !scales || M <= 0 || K <= 0 || K % 32) return SA_ERR_ARG;
+  if (ldx < K || ldx % 8 || ldq < K || ldq % 8 || lds < K / 32) return SA_ERR_ARG;
+  if ((((uintptr_t)x) & 15) || (((uintptr_t)q) & 7)) return SA_ERR_ARG;
+  QuantArgs a{(const bf16*)x, ldx, (uint8_t*)q, ldq, (uint8_t*)scales, lds, M, K};
+  hipLaunchKernelGGL(mxfp8_quant_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                             const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
+                             void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
+                             int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream) {
+  if (!A || !A_scales || !W || !W_scales || !C || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
+  if (K % BKB != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 || ldws < K / 32)
+    return SA_ERR_ARG;
+  if ((((uintptr_t)A) & 15) || (((uintptr_t)W) & 15)) return SA_ERR_ARG;
+  // a K-tile's four scale bytes of a row are fetched as one dword
+  if (ldas % 4 != 0 || ldws % 4 != 0 || (((uintptr_t)A_scales) & 3) || (((uintptr_t)W_scales) & 3)) return SA_ERR_ARG;
+  // 32-bit element / scale offsets inside the kernel
+  if ((long)M * lda >= 0x7fffffffL || (long)N * ldw >= 0x7fffffffL || (long)M * ldas >= 0x7fffffffL ||
+      (long)N * ldws >= 0x7fffffffL)
+    return SA_ERR_ARG;
+  if (ldc < N || ldc % 4 != 0 || (((uintptr_t)C) & 15)) return SA_ERR_ARG;  // 4-column vector stores
+  if (epilogue == EPI_RES_F32 &&
+      (!residual || ldr % 4 != 0 || (((uintptr_t)residual) & 15) || (gate && rows_per_batch <= 0))) return SA_ERR_ARG;
+  if (epilogue == EPI_RES_F32 && gate && ((gate_bstride % 4 != 0) || (((uintptr_t)gate) & 15))) return SA_ERR_ARG;
+  if (epilogue == EPI_GELU_MXFP8 && (N % 32 != 0 || !C_scales || ldcs < N / 32)) return SA_ERR_ARG;
+  MxArgs g{(const uint8_t*)A, lda, (const uint8_t*)A_scales, ldas, (const uint8_t*)W, ldw, (const uint8_t*)W_scales, ldws,
+           bias, C, ldc, (uint8_t*)C_scales, ldcs, residual, ldr, gate, gate_bstride,
+           rows_per_batch > 0 ? rows_per_batch : 1, M, N, K, epilogue == EPI_RES_F32 ? 4 : 8};
+  hipStream_t st = (hipStream_t)stream;
+  switch (epilogue) {
+    case EPI_BF16: return launch<EPI_BF16>(g, st);
+    case EPI_GELU_BF16: return launch<EPI_GELU_BF16>(g, st);
+    case EPI_F32: return launch<EPI_F32>(g, st);
+    case EPI_RES_F32: return launch<EPI_RES_F32>(g, st);
+    case EPI_GELU_MXFP8: return launch<EPI_GELU_MXFP8>(g, st);
+    default: return SA_ERR_ARG;
+  }
+}

@@ -6,7 +6,7 @@
 //  * sa_qk_rmsnorm_rope: WanRMSNorm over the FULL model dim on q and k (1B:326-342,395-396),
 //    then the 3-D complex RoPE (1B:295-323) with fp64-derived fp32 (cos,sin) tables; tokens past
 //    f*h*w (padding) are left unrotated (1B:319).  In place on the fused QKV GEMM output.
-#include "common.h"
+#include "mxfp8.h"
 #include <cstdlib>
 
 #ifndef SA_LN_SHARED_DEFAULT
@@ -43,9 +43,13 @@ __device__ __forceinline__ void store8<bf16>(bf16* p, const float* v) {
   *(bf16x8*)p = a;
 }
 
+// output type tag of sa_layernorm_mod_mxfp8: e4m3fn element bytes in out, E8M0 scale bytes in sout
+struct mx8 { uint8_t b; };
+
 struct LnArgs {
   const void* x; long ldx;
   void* out; long ldo;
+  uint8_t* sout; long lds;                 // MXFP8 output only: scale bytes [M][lds], byte c / 32 of a row
   const float* w; const float* b;         // affine (optional)
   const float* shift; const float* scale; long mod_bstride;  // AdaLN (optional)
   const float* gate;                       // gated residual (optional, f32 out only)
@@ -53,6 +57,27 @@ struct LnArgs {
   int M, C;
   float eps;
 };
+
+// store the 8 output columns c0.. of `row` held by this lane (out = the row's first element)
+template <typename TO>
+__device__ __forceinline__ void store_cols8(const LnArgs&, TO* out, int, int c0, const float* y) {
+  store8<TO>(out + c0, y);
+}
+// MXFP8: the bf16-rounded values quantised (= bf16 output followed by sa_mxfp8_quant); the 32-column block is the
+// four adjacent lanes c0 / 8 .. (C % 32 == 0, so they are active together)
+template <>
+__device__ __forceinline__ void store_cols8<mx8>(const LnArgs& a, mx8* out, int row, int c0, const float* y) {
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(y[j]));
+  float amax = mx_amax8(v);
+  amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+  uint32_t s;
+  const u32x2 q = mx_quant8(v, amax, &s);
+  *(u32x2*)((uint8_t*)out + c0) = q;
+  if ((c0 & 31) == 0) a.sout[(long)row * a.lds + c0 / 32] = (uint8_t)s;
+}
 
 constexpr int MAXV = 10;  // up to 10 chunks of 8 per lane -> C <= 5120 (the 14B DiT width)
 
@@ -109,7 +134,7 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(LnArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) y[j] = __builtin_fmaf(y[j], g8[j], v[i][j]);
       }
-      store8<TO>(out + c0, y);
+      store_cols8<TO>(a, out, row, c0, y);
     }
 }
 
@@ -426,7 +451,7 @@ __global__ __launch_bounds__(NW * 64) void layernorm_mod_shared_kernel(LnArgs a)
 #pragma unroll
       for (int j = 0; j < 8; ++j) y[j] = __builtin_fmaf(y[j], g8[j], v[i][j]);
     }
-    store8<TO>(out + c0, y);
+    store_cols8<TO>(a, out, row, c0, y);
   }
 }
 
@@ -474,13 +499,30 @@ extern "C" int sa_layernorm_mod(const void* x, int64_t ldx, int in_dtype, void* 
   if ((shift == nullptr) != (scale == nullptr)) return SA_ERR_ARG;
   if ((scale || gate) && rows_per_batch <= 0) return SA_ERR_ARG;
   if (gate && (out_dtype != 0 || !scale)) return SA_ERR_ARG;
-  LnArgs a{x, ldx, out, ldo, weight, bias, shift, scale, mod_bstride, gate, rows_per_batch > 0 ? rows_per_batch : 1,
-           M, C, eps};
+  LnArgs a{x, ldx, out, ldo, nullptr, 0, weight, bias, shift, scale, mod_bstride, gate,
+           rows_per_batch > 0 ? rows_per_batch : 1, M, C, eps};
   hipStream_t st = (hipStream_t)stream;
   if (in_dtype == 0 && out_dtype == 1) return launch_ln<float, bf16>(a, st);
   if (in_dtype == 0 && out_dtype == 0) return launch_ln<float, float>(a, st);
   if (in_dtype == 1 && out_dtype == 1) return launch_ln<bf16, bf16>(a, st);
   if (in_dtype == 1 && out_dtype == 0) return launch_ln<bf16, float>(a, st);
+  return SA_ERR_ARG;
+}
+
+// sa_layernorm_mod with bf16 output followed by sa_mxfp8_quant, in one pass (no gated residual: that one is fp32)
+extern "C" int sa_layernorm_mod_mxfp8(const void* x, int64_t ldx, int in_dtype, void* out, int64_t ldo, void* out_scales,
+                                      int64_t lds, const float* weight, const float* bias, const float* shift,
+                                      const float* scale, int64_t mod_bstride, int rows_per_batch, int M, int C,
+                                      float eps, void* stream) {
+  if (!x || !out || !out_scales || M <= 0 || C <= 0 || C % 32 || C > 512 * MAXV || ldx % 8 || ldo % 8) return SA_ERR_ARG;
+  if (ldo < C || lds < C / 32 || (((uintptr_t)out) & 7)) return SA_ERR_ARG;
+  if ((shift == nullptr) != (scale == nullptr)) return SA_ERR_ARG;
+  if (scale && rows_per_batch <= 0) return SA_ERR_ARG;
+  LnArgs a{x, ldx, out, ldo, (uint8_t*)out_scales, lds, weight, bias, shift, scale, mod_bstride, nullptr,
+           rows_per_batch > 0 ? rows_per_batch : 1, M, C, eps};
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == 0) return launch_ln<float, mx8>(a, st);
+  if (in_dtype == 1) return launch_ln<bf16, mx8>(a, st);
   return SA_ERR_ARG;
 }
 

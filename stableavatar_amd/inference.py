@@ -17,6 +17,8 @@ Flag mapping:
   the CPU-offload modes keep the models resident (288 GB of HBM holds every model) and say so;
 * ``--enable_teacache`` / ``--teacache_threshold`` / ``--num_skip_start_steps`` / ``--teacache_offload``:
   ``transformer.enable_teacache`` with the reference's coefficient table;
+* ``--fp8_ffn`` (no counterpart in the reference): ``transformer.enable_fp8_ffn()``, the DiT blocks' FFN GEMMs on
+  MXFP8 operands (DESIGN.md "fp8 FFN"); changes numerics; combines with every flag above;
 * ``--fsdp_dit`` / ``--t5_fsdp`` / ``--t5_cpu`` / ``--offload_model``: accepted, no effect (the 3.5 GB DiT is
   replicated).
 Audio is read with scipy (16-bit / float WAV, channels averaged, polyphase resampling to 16 kHz) where the
@@ -78,6 +80,11 @@ def parse_args(argv=None):
     # MI355X build additions
     p.add_argument("--device", type=str, default=None, help="default cuda:LOCAL_RANK")
     p.add_argument("--dtype", type=str, default="bf16", choices=("bf16",), help="DiT compute dtype (as the reference)")
+    p.add_argument("--fp8_ffn", action="store_true",
+                   help="run the DiT blocks' FFN GEMMs on MXFP8 operands (block-scaled e4m3, fp32 accumulation; "
+                        "WanTransformer3DFantasyModel.enable_fp8_ffn). Changes numerics (about 0.7e-2 rel-L2 per "
+                        "forward on top of bf16) and has no counterpart in the reference. Measured: the FFN's three "
+                        "kernels 1.15x, the 30-layer forward 1.04x (DESIGN.md, fp8 FFN).")
     p.add_argument("--window_parallel", action="store_true",
                    help="multi-GPU: spread the sliding windows of each step over the ranks instead of sequence "
                         "parallelism (long clips, SURVEY.md §8(e))")
@@ -241,6 +248,9 @@ def main(argv=None):
         else:
             transformer3d.enable_multi_gpus_inference()
         pipeline.enable_vae_parallel(args.vae_parallel)
+    if args.fp8_ffn:
+        print("fp8 FFN: the DiT blocks' FFN GEMMs run on MXFP8 operands (numerics differ from the bf16 path)")
+        transformer3d.enable_fp8_ffn()
     if args.enable_teacache:
         coefficients = get_teacache_coefficients(root)
         if coefficients is not None:

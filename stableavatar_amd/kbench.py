@@ -1,5 +1,7 @@
 """Kernel micro-benchmarks at the config-2 (512x512x81f, CFG batch 3) shapes of the DiT.
-python -m stableavatar_amd.kbench  -> one JSON line per kernel with TFLOP/s (random data)."""
+python -m stableavatar_amd.kbench  -> one JSON line per kernel with TFLOP/s (random data).
+Selectors: gemm, attn, gemmvar, attnvar, dit, ditvar, ...; gemmfp8 = the fp8 FFN mode's LayerNorm / ffn_up / ffn_down
+against the bf16 kernels, ditfp8 = the whole forward with the mode off and on."""
 from __future__ import annotations
 
 import json
@@ -104,6 +106,8 @@ def main(which=("gemm", "attn")):
             res.append(r)
             print(json.dumps(r), flush=True)
             del x, w, out
+    if "gemmfp8" in which:  # the fp8 FFN mode's kernels against the bf16 ones they replace, interleaved rounds
+        res.extend(bench_fp8_ffn(M))
     if "attnvar" in which:
         import os
         L, H, D = 21504, 12, 128
@@ -272,11 +276,64 @@ def main(which=("gemm", "attn")):
         res.append(bench_dit(env_variants=tuple(os.environ.get("SA_KB_ENVVARS", "SA_LN_SHARED=0,SA_LN_SHARED=8")
                                                 .split(","))))
         print(json.dumps(res[-1]), flush=True)
+    if "ditfp8" in which:  # whole-forward A/B of enable_fp8_ffn(), interleaved
+        res.append(bench_dit(fp8_ab=True))
+        print(json.dumps(res[-1]), flush=True)
     if "ditvar" in which:  # in-situ A/B of attention variants inside full DiT forwards (interleaved)
         import os
         avars = tuple(int(v) for v in os.environ.get("SA_KB_AVARS", "1").split(","))
         res.append(bench_dit(attn_variants=avars))
         print(json.dumps(res[-1]), flush=True)
+    return res
+
+
+def bench_fp8_ffn(M=3 * 21504, C=1536, FF=8960, rpb=21504):
+    """The three kernels of a block's FFN at config 2 (M = 64 512 rows), bf16 (auto kernel) vs MXFP8, same process,
+    interleaved rounds, median of 3: LayerNorm + modulate (bf16 out vs MXFP8 out), ffn_up (N 8960, K 1536, GELU;
+    MXFP8 out in the fp8 mode) and ffn_down (N 1536, K 8960, gated residual in place).  One JSON line per pair
+    and one for the sum; ratio = bf16 ms / MXFP8 ms (> 1: the fp8 kernel is faster)."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(M, C, device=dev, generator=g)
+    mod = torch.randn(3, 2, C, device=dev, generator=g) * 0.3
+    w0 = (torch.randn(FF, C, device=dev, generator=g) / C ** 0.5).bfloat16()
+    w2 = (torch.randn(C, FF, device=dev, generator=g) / FF ** 0.5).bfloat16()
+    b0, b2 = torch.randn(FF, device=dev, generator=g) * 0.1, torch.randn(C, device=dev, generator=g) * 0.1
+    gate = torch.randn(3, C, device=dev, generator=g)
+    w0q, w2q = ops.mxfp8_quant(w0), ops.mxfp8_quant(w2)
+    ln_bf, ln_mx = torch.empty(M, C, device=dev, dtype=torch.bfloat16), ops.Mx8.empty(M, C, dev)
+    h_bf, h_mx = torch.empty(M, FF, device=dev, dtype=torch.bfloat16), ops.Mx8.empty(M, FF, dev)
+    out = torch.zeros(M, C, device=dev)
+    kw = dict(shift=mod[:, 0], scale=mod[:, 1], rows_per_batch=rpb)
+    pairs = {
+        "layernorm": (lambda: ops.layernorm_mod(x, ln_bf, 1e-6, **kw), lambda: ops.layernorm_mod_mxfp8(x, ln_mx, 1e-6, **kw)),
+        "ffn_up": (lambda: ops.linear(ln_bf, w0, b0, ops.EPI_GELU_TANH_BF16, out=h_bf),
+                   lambda: ops.linear_mxfp8(ln_mx, w0q, b0, ops.EPI_GELU_TANH_MXFP8, out=h_mx)),
+        "ffn_down": (lambda: ops.linear(h_bf, w2, b2, ops.EPI_RES_F32, out=out, residual=out, gate=gate, rows_per_batch=rpb),
+                     lambda: ops.linear_mxfp8(h_mx, w2q, b2, ops.EPI_RES_F32, out=out, residual=out, gate=gate,
+                                              rows_per_batch=rpb)),
+    }
+    res, tot = [], [0.0, 0.0]
+    for name, fns in pairs.items():  # in data-flow order: each pair's inputs were written by the pair before
+        times = ([], [])
+        for _ in range(3):
+            for i, fn in enumerate(fns):
+                if name == "ffn_down":
+                    out.zero_()
+                times[i].append(_time(fn, iters=40, warmup=2))
+        ms = [sorted(t)[1] for t in times]
+        r = {"kernel": f"fp8ffn_{name}", "M": M, "bf16_ms": round(ms[0], 4), "mxfp8_ms": round(ms[1], 4),
+             "ratio": round(ms[0] / ms[1], 3)}
+        if name != "layernorm":
+            fl = 2.0 * M * C * FF
+            r.update(bf16_tflops=round(fl / ms[0] / 1e9, 1), mxfp8_tflops=round(fl / ms[1] / 1e9, 1))
+        tot = [tot[0] + ms[0], tot[1] + ms[1]]
+        res.append(r)
+        print(json.dumps(r), flush=True)
+    r = {"kernel": "fp8ffn_ln_up_down", "M": M, "bf16_ms": round(tot[0], 4), "mxfp8_ms": round(tot[1], 4),
+         "ratio": round(tot[0] / tot[1], 3)}
+    res.append(r)
+    print(json.dumps(r), flush=True)
     return res
 
 
@@ -374,9 +431,11 @@ def attn_clip_inputs(layers=(0, 15, 29)):
     return out
 
 
-def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False):
+def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False):
     """One full 30-layer DiT forward at config 2 (B=3 CFG, 21 latent frames at 64x64, L=21504).
-    attn_variants: time the forward under each self-attention schedule, interleaved rounds."""
+    attn_variants: time the forward under each self-attention schedule, interleaved rounds.
+    fp8_ab: the forward with enable_fp8_ffn() off and on (two models on the same weights), interleaved rounds,
+    and the rel-L2 between their outputs."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -400,6 +459,24 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False):
         return fwd
     from .flops import dit_forward_flops
     fl = dit_forward_flops()
+    if fp8_ab:
+        m8 = WanTransformer3DFantasyModel(**cfg)
+        m8.load_state_dict(m.state_dict())
+        m8 = m8.to(dev)
+        m8.enable_fp8_ffn()
+        fwds = {"bf16": fwd, "fp8_ffn": lambda: m8.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)}
+        times = {k: [] for k in fwds}
+        with torch.no_grad():
+            for _ in range(3):
+                for k, f in fwds.items():
+                    times[k].append(_time(f, iters=2, warmup=1))
+            o, o8 = fwds["bf16"]().float(), fwds["fp8_ffn"]().float()
+        r = {"kernel": "dit_forward_fp8_ffn_ab", "tflop": round(fl / 1e12, 1),
+             "rel_l2_on_vs_off": round(((o8 - o).norm() / o.norm()).item(), 5)}
+        for k in fwds:
+            r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
+        r["ratio"] = round(r["bf16_ms"] / r["fp8_ffn_ms"], 4)
+        return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os
         times = {v: [] for v in env_variants}

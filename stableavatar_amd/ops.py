@@ -11,6 +11,7 @@ import torch
 from ._lib import call
 
 EPI_BF16, EPI_GELU_TANH_BF16, EPI_F32, EPI_RES_F32, EPI_GELU_ERF_BF16, EPI_SILU_F32, EPI_BF16_T, EPI_BF16_TP32 = range(8)
+EPI_GELU_TANH_MXFP8 = 8  # linear_mxfp8 only
 F32, BF16 = 0, 1
 
 
@@ -182,6 +183,91 @@ def layernorm_mod(x, out, eps, weight=None, bias=None, shift=None, scale=None, g
         assert shift.stride(0) == mstride
     call("sa_layernorm_mod", x.data_ptr(), x.stride(0), _dt(x), out.data_ptr(), out.stride(0), _dt(out), _p(weight),
          _p(bias), _p(shift), _p(scale), mstride, _p(gate), rows_per_batch, M, C, float(eps), _stream())
+    return out
+
+
+class Mx8:
+    """An MXFP8 matrix (stableavatar_amd/mxfp8.py): q uint8 [M, K] e4m3fn bytes, s uint8 [M, K / 32] E8M0 scales."""
+    __slots__ = ("q", "s")
+
+    def __init__(self, q, s):
+        assert q.dtype == torch.uint8 and s.dtype == torch.uint8 and q.stride(1) == 1 and s.stride(1) == 1
+        assert q.shape[0] == s.shape[0] and q.shape[1] == 32 * s.shape[1]
+        self.q, self.s = q, s
+
+    @classmethod
+    def empty(cls, M, K, device):
+        return cls(torch.empty(M, K, device=device, dtype=torch.uint8),
+                   torch.empty(M, K // 32, device=device, dtype=torch.uint8))
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    def __getitem__(self, rows):
+        """a row range (both arrays)"""
+        return Mx8(self.q[rows], self.s[rows])
+
+
+def mxfp8_quant(x, out=None):
+    """bf16 x [M, K] (K % 32 == 0) -> Mx8, bit-identical to mxfp8.quantize (sa_mxfp8_quant)."""
+    _check(x, torch.bfloat16, "mxfp8_quant.x")
+    M, K = x.shape
+    assert x.stride(1) == 1
+    if out is None:
+        out = Mx8.empty(M, K, x.device)
+    call("sa_mxfp8_quant", x.data_ptr(), x.stride(0), out.q.data_ptr(), out.q.stride(0), out.s.data_ptr(),
+         out.s.stride(0), M, K, _stream())
+    return out
+
+
+def layernorm_mod_mxfp8(x, out, eps, weight=None, bias=None, shift=None, scale=None, rows_per_batch=0):
+    """layernorm_mod with bf16 output followed by mxfp8_quant, in one kernel; out: Mx8 [M, C]."""
+    M, C = x.shape
+    mstride = 0
+    if scale is not None:
+        mstride = scale.stride(0)
+        assert shift.stride(0) == mstride
+    call("sa_layernorm_mod_mxfp8", x.data_ptr(), x.stride(0), _dt(x), out.q.data_ptr(), out.q.stride(0),
+         out.s.data_ptr(), out.s.stride(0), _p(weight), _p(bias), _p(shift), _p(scale), mstride, rows_per_batch, M, C,
+         float(eps), _stream())
+    return out
+
+
+def linear_mxfp8(x, weight, bias=None, epilogue=EPI_BF16, out=None, residual=None, gate=None, rows_per_batch=0):
+    """y = epi(deq(x) @ deq(weight)^T + bias) on the block-scaled fp8 MFMA (sa_gemm_mxfp8).  x: Mx8 [M, K],
+    weight: Mx8 [N, K], K % 128 == 0.  epilogue: EPI_BF16 / EPI_GELU_TANH_BF16 / EPI_F32 / EPI_RES_F32 as linear(),
+    or EPI_GELU_TANH_MXFP8 (out: Mx8 [M, N] = the bf16 GELU output quantised, N % 32 == 0)."""
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape[1] != K:
+        raise ValueError(f"linear_mxfp8: x K = {K}, weight K = {weight.shape[1]}")
+    if bias is not None:
+        _check(bias, torch.float32, "linear_mxfp8.bias")
+    cs = cs_ld = 0
+    if epilogue == EPI_GELU_TANH_MXFP8:
+        if out is None:
+            out = Mx8.empty(M, N, x.q.device)
+        if tuple(out.shape) != (M, N):
+            raise ValueError(f"linear_mxfp8: out shape {tuple(out.shape)} != {(M, N)}")
+        c, cs, cs_ld = out.q, out.s.data_ptr(), out.s.stride(0)
+    else:
+        dt = torch.float32 if epilogue in (EPI_F32, EPI_RES_F32) else torch.bfloat16
+        if out is None:
+            out = torch.empty(M, N, device=x.q.device, dtype=dt)
+        if out.dtype != dt or out.stride(1) != 1 or tuple(out.shape) != (M, N):
+            raise ValueError(f"linear_mxfp8: out must be {dt} [{M}, {N}]")
+        c = out
+    ldr = gstride = 0
+    if epilogue == EPI_RES_F32:
+        assert residual is not None and residual.dtype == torch.float32
+        ldr = residual.stride(0)
+        if gate is not None:
+            assert gate.dtype == torch.float32 and gate.stride(-1) == 1
+            gstride = gate.stride(0)
+    call("sa_gemm_mxfp8", x.q.data_ptr(), x.q.stride(0), x.s.data_ptr(), x.s.stride(0), weight.q.data_ptr(),
+         weight.q.stride(0), weight.s.data_ptr(), weight.s.stride(0), _p(bias), c.data_ptr(), c.stride(0), cs, cs_ld,
+         M, N, K, epilogue, _p(residual), ldr, _p(gate), gstride, rows_per_batch, _stream())
     return out
 
 

@@ -225,6 +225,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         self.teacache = None  # enable_teacache() (1B:867)
         self._riflex = None  # enable_riflex() (1B:890-905)
         self.attn_kernel = 0  # self-attention schedule (sa_attn_fwd_ex; 0 = auto), for in-situ A/B
+        self._fp8_ffn = False  # enable_fp8_ffn(): the blocks' FFN GEMMs on MXFP8 operands
         self._packed = None
         self._ws = {}
         self._ctx_cache = None
@@ -317,6 +318,20 @@ class WanTransformer3DFantasyModel(nn.Module):
     def disable_teacache(self):
         self.teacache = None
 
+    def enable_fp8_ffn(self, enabled=True):
+        """MI355X addition (no counterpart in the reference; changes numerics): the FFN of every DiT block --
+        norm2 + modulate, ffn.0 + GELU, ffn.2 + gated residual (1B:687-691) -- runs its two GEMMs on MXFP8 operands
+        (stableavatar_amd/mxfp8.py; block-scaled e4m3 MFMA, fp32 accumulation).  Everything else, the vocal
+        projector's FFN included, stays bf16.  Toggling drops the packed weights and the workspace: the next forward
+        re-packs (ffn.0 / ffn.2 quantised from the same bf16 weights the bf16 path packs)."""
+        enabled = bool(enabled)
+        if enabled and (self.dim % 128 or self.ffn_dim % 128):
+            raise ValueError(f"enable_fp8_ffn: dim {self.dim} and ffn_dim {self.ffn_dim} must be multiples of 128")
+        if enabled != self._fp8_ffn:
+            self._fp8_ffn = enabled
+            self._packed = None
+            self._ws = {}
+
     def enable_multi_gpus_inference(self, group=None, loopback=None):
         """Ulysses sequence parallelism over torch.distributed (RCCL); replaces the xfuser path
         installed at 1B:918-923 with single-GPU semantics.  loopback=True (default: env
@@ -394,6 +409,8 @@ class WanTransformer3DFantasyModel(nn.Module):
             L.w_co, L.b_co = bf(c + "o.weight"), f32(c + "o.bias")
             L.w_f0, L.b_f0 = bf(p + "ffn.0.weight"), f32(p + "ffn.0.bias")
             L.w_f2, L.b_f2 = bf(p + "ffn.2.weight"), f32(p + "ffn.2.bias")
+            if self._fp8_ffn:  # the bf16 weights quantised on the GPU (= mxfp8.quantize), the bf16 copies dropped
+                L.w_f0, L.w_f2 = ops.mxfp8_quant(L.w_f0), ops.mxfp8_quant(L.w_f2)
             pk.layers.append(L)
         pk.head_mod = f32("head.modulation").reshape(1, 2, dim)
         pk.w_head, pk.b_head = bf("head.head.weight"), f32("head.head.bias")
@@ -445,9 +462,12 @@ class WanTransformer3DFantasyModel(nn.Module):
                 mod=torch.empty(M, dim, device=dev, dtype=torch.bfloat16),
                 qkv=torch.empty(M, 3 * dim, device=dev, dtype=torch.bfloat16),
                 att=torch.empty(M, dim, device=dev, dtype=torch.bfloat16),
-                ffn=torch.empty(M, self.ffn_dim, device=dev, dtype=torch.bfloat16),
+                ffn=torch.empty(M, self.ffn_dim, device=dev, dtype=torch.bfloat16) if not self._fp8_ffn else None,
                 vt=None,  # V^T [dim, M rounded up to 64] of the single-GPU self-attention, allocated on first use
             )
+            if self._fp8_ffn:  # the FFN's operands as MXFP8: its LayerNorm output and its hidden activations
+                ws.modq = ops.Mx8.empty(M, dim, dev)
+                ws.ffn = ops.Mx8.empty(M, self.ffn_dim, dev)
             self._ws = {key: ws}  # keep one shape at a time
         return ws
 
@@ -662,10 +682,22 @@ class WanTransformer3DFantasyModel(nn.Module):
                         ops.attention(qc, kvi[:, :dim], kvi[:, dim:], att, s_img, 1, Lc, H_, accumulate=True)
                     ops.attention(qc, kvv[:, :dim], kvv[:, dim:], att, s_voc, n_voc, q_voc, H_, accumulate=True)
                 ops.linear(att, L.w_co, L.b_co, ops.EPI_RES_F32, out=xr, residual=xr)
-                ops.layernorm_mod(xr, mod, eps, shift=em[b:b + 1, 3], scale=em[b:b + 1, 4], rows_per_batch=Lc)
-                ops.linear(mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_BF16, out=ws.ffn[rs])
-                ops.linear(ws.ffn[rs], L.w_f2, L.b_f2, ops.EPI_RES_F32, out=xr, residual=xr, gate=em[b:b + 1, 5],
-                           rows_per_batch=Lc)
+                self._ffn(L, xr, ws, rs, em[b:b + 1, 3], em[b:b + 1, 4], em[b:b + 1, 5], Lc)
+
+    def _ffn(self, L, x, ws, rows, shift, scale, gate, Lc):
+        """The FFN third of a block (1B:687-691) on the rows x of the residual stream (workspace rows `rows`): norm2 +
+        modulate, ffn.0 + GELU, ffn.2 + gated residual into x.  With enable_fp8_ffn() the LayerNorm writes MXFP8,
+        ffn.0's epilogue hands ffn.2 its operand as MXFP8 and both GEMMs run on the block-scaled fp8 MFMA."""
+        if self._fp8_ffn:
+            mod, ffn = ws.modq[rows], ws.ffn[rows]
+            ops.layernorm_mod_mxfp8(x, mod, self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
+            ops.linear_mxfp8(mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_MXFP8, out=ffn)
+            ops.linear_mxfp8(ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=gate, rows_per_batch=Lc)
+            return
+        mod, ffn = ws.mod[rows], ws.ffn[rows]
+        ops.layernorm_mod(x, mod, self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
+        ops.linear(mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_BF16, out=ffn)
+        ops.linear(ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=gate, rows_per_batch=Lc)
 
     # ------------------------------------------------------------------ timing hooks (bench.py)
 
@@ -1031,9 +1063,7 @@ class WanTransformer3DFantasyModel(nn.Module):
                     ops.attention(qc, kvv[:, :dim], kvv[:, dim:], ws.att, segs_voc, voc_n, voc_q, H_, accumulate=True)
                 ops.linear(ws.att, L.w_co, L.b_co, ops.EPI_RES_F32, out=x, residual=x)
                 # FFN (1B:687-691)
-                ops.layernorm_mod(x, ws.mod, self.eps, shift=em[:, 3], scale=em[:, 4], rows_per_batch=Lc)
-                ops.linear(ws.mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_BF16, out=ws.ffn)
-                ops.linear(ws.ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=em[:, 5], rows_per_batch=Lc)
+                self._ffn(L, x, ws, slice(None), em[:, 3], em[:, 4], em[:, 5], Lc)
             if sp_streams:
                 for rs_ in rstreams:
                     main.wait_stream(rs_)
