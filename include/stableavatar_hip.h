@@ -172,6 +172,39 @@ int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas
                   int64_t ldcs, int M, int N, int K, int epilogue, const float* residual, int64_t ldr,
                   const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream);
 
+/* ---- MXFP8 self-attention (opt-in fp8 attention mode; no counterpart in the reference) ----
+ * WanSelfAttention's attention (wan_fantasy_transformer3d_1B.py:383-413) with both products on MXFP8 operands.
+ * stableavatar_amd/mxfp8_attn.py is the definition.  head_dim 128 only.  segs is sa_attn_fwd's table
+ * {q_row0, q_len, kv_row0, kv_len}; vcol0 (device int32 per segment, multiples of 128, host-computed) is the first
+ * V^T column of each segment, which owns ceil128(kv_len) columns of the Rv (a multiple of 128). */
+
+/* k_mean[seg][heads * 128] (fp32) = the column means of bf16 k over the segment's kv_len rows (0 for an empty
+ * segment).  Two passes through work (>= nseg * 16 * heads * 128 floats), no atomics: deterministic for a fixed
+ * launch.  k 16-B aligned, k_stride % 8 == 0. */
+int sa_attn_kmean(const void* k, int64_t k_stride, const int32_t* segs, int nseg, int heads, int head_dim,
+                  float* k_mean, float* work, void* stream);
+
+/* bf16 q, k, v rows (each with its own stride: column slices of a QKV buffer or separate tensors; strides % 8 == 0,
+ * 16-B aligned) -> the three operands, bit for bit the definition's:
+ *   q_out [rows][heads * 128] = quant(fp32(q) * (scale * log2 e)) along D, q_scales [rows][heads * 4];
+ *   k_out / k_scales likewise = quant(fp32(k) - k_mean[seg][column]) (k_mean NULL: no subtraction);
+ *   vt_out [heads * 128][Rv] / vt_scales [heads * 128][Rv / 32]: V^T in the P^T operand's position order, quantised
+ *   along 32 consecutive positions, keys past kv_len zeros.
+ * Rows follow the inputs' row numbers; rows outside every segment are left untouched. */
+int sa_attn_pack_mxfp8(const void* q, int64_t q_stride, const void* k, int64_t k_stride, const void* v,
+                       int64_t v_stride, const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len,
+                       int max_kv_len, int heads, int head_dim, float scale, const float* k_mean, void* q_out,
+                       void* q_scales, void* k_out, void* k_scales, void* vt_out, void* vt_scales, int64_t Rv,
+                       void* stream);
+
+/* Flash attention on the operands of sa_attn_pack_mxfp8 (v_mfma_scale_f32_16x16x128_f8f6f4, fp32 softmax and
+ * accumulation), bf16 out; o_rows as sa_attn_fwd_map (NULL = the query's own row).  kv_len == 0 writes zeros.  A
+ * segment whose V^T columns would run past Rv is skipped.  o_stride % 8 == 0, operands 16-B aligned. */
+int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void* k, const void* k_scales, const void* vt,
+                      const void* vt_scales, int64_t Rv, void* o, int64_t o_stride, const int32_t* segs,
+                      const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim, const int32_t* o_rows,
+                      void* stream);
+
 /* WanRMSNorm over the full width on q (and k) + rope_apply (1B:295-342, :395-396, :403-404) in place.
  * rope = fp32 [1024][head_dim/2][2] (cos, sin) table or NULL (no rotation); token index
  * t = tok_offset + row % rows_per_batch; t >= F*H*W is not rotated (padding, 1B:319). */

@@ -27,6 +27,9 @@ SIGNATURES = {
     "sa_mxfp8_quant": "plplpliip",
     "sa_layernorm_mod_mxfp8": "pliplplppppliiifp",
     "sa_gemm_mxfp8": "plplplplpplpliiiiplplip",
+    "sa_attn_kmean": "plpiiippp",
+    "sa_attn_pack_mxfp8": "plplplppiiiiifppppppplp",
+    "sa_attn_fwd_mxfp8": "pppppplplppiiiipp",
     "sa_qk_rmsnorm_rope": "pliippiiifpiiiiiiip",
     "sa_qkv_pack": "plppiiifpiiiiiiipiiiip",
     "sa_patch_im2col": "plllipllliiiiipiip",

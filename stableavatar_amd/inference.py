@@ -19,6 +19,8 @@ Flag mapping:
   ``transformer.enable_teacache`` with the reference's coefficient table;
 * ``--fp8_ffn`` (no counterpart in the reference): ``transformer.enable_fp8_ffn()``, the DiT blocks' FFN GEMMs on
   MXFP8 operands (DESIGN.md "fp8 FFN"); changes numerics; combines with every flag above;
+* ``--fp8_attn`` (no counterpart in the reference): ``transformer.enable_fp8_attention()``, the DiT blocks'
+  self-attention on MXFP8 operands (DESIGN.md "fp8 attention"); changes numerics; combines with every flag above;
 * ``--fsdp_dit`` / ``--t5_fsdp`` / ``--t5_cpu`` / ``--offload_model``: accepted, no effect (the 3.5 GB DiT is
   replicated).
 Audio is read with scipy (16-bit / float WAV, channels averaged, polyphase resampling to 16 kHz) where the
@@ -85,6 +87,13 @@ def parse_args(argv=None):
                         "WanTransformer3DFantasyModel.enable_fp8_ffn). Changes numerics (about 0.7e-2 rel-L2 per "
                         "forward on top of bf16) and has no counterpart in the reference. Measured: the FFN's three "
                         "kernels 1.15x, the 30-layer forward 1.04x (DESIGN.md, fp8 FFN).")
+    p.add_argument("--fp8_attn", action="store_true",
+                   help="run the DiT blocks' self-attention (Q K^T and P V) on MXFP8 operands (block-scaled e4m3, "
+                        "fp32 softmax and accumulation; WanTransformer3DFantasyModel.enable_fp8_attention). Changes "
+                        "numerics (about 0.2e-2 rel-L2 per forward on synthetic weights, 1.0e-2 with scores four "
+                        "times as sharp; real checkpoints unmeasured) and has no counterpart in the reference. "
+                        "Measured: the self-attention launch 1.38x with its operand pack included, the 30-layer "
+                        "forward 1.10x, 1.25x together with --fp8_ffn (DESIGN.md, fp8 attention).")
     p.add_argument("--window_parallel", action="store_true",
                    help="multi-GPU: spread the sliding windows of each step over the ranks instead of sequence "
                         "parallelism (long clips, SURVEY.md §8(e))")
@@ -251,6 +260,10 @@ def main(argv=None):
     if args.fp8_ffn:
         print("fp8 FFN: the DiT blocks' FFN GEMMs run on MXFP8 operands (numerics differ from the bf16 path)")
         transformer3d.enable_fp8_ffn()
+    if args.fp8_attn:
+        print("fp8 attention: the DiT blocks' self-attention runs on MXFP8 operands (numerics differ from the bf16 "
+              "path)")
+        transformer3d.enable_fp8_attention()
     if args.enable_teacache:
         coefficients = get_teacache_coefficients(root)
         if coefficients is not None:

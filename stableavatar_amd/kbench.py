@@ -1,7 +1,9 @@
 """Kernel micro-benchmarks at the config-2 (512x512x81f, CFG batch 3) shapes of the DiT.
 python -m stableavatar_amd.kbench  -> one JSON line per kernel with TFLOP/s (random data).
 Selectors: gemm, attn, gemmvar, attnvar, dit, ditvar, ...; gemmfp8 = the fp8 FFN mode's LayerNorm / ffn_up / ffn_down
-against the bf16 kernels, ditfp8 = the whole forward with the mode off and on."""
+against the bf16 kernels, ditfp8 = the whole forward with the mode off and on; attnfp8 = the config-2 self-attention
+launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the whole forward with that mode off, on, and
+on together with the fp8 FFN."""
 from __future__ import annotations
 
 import json
@@ -276,6 +278,11 @@ def main(which=("gemm", "attn")):
         res.append(bench_dit(env_variants=tuple(os.environ.get("SA_KB_ENVVARS", "SA_LN_SHARED=0,SA_LN_SHARED=8")
                                                 .split(","))))
         print(json.dumps(res[-1]), flush=True)
+    if "attnfp8" in which:  # the fp8 attention mode's kernels against the bf16 launch, interleaved rounds
+        res.extend(bench_fp8_attn())
+    if "ditfp8attn" in which:  # whole-forward A/B of enable_fp8_attention() (and with enable_fp8_ffn()), interleaved
+        res.append(bench_dit(fp8_attn_ab=True))
+        print(json.dumps(res[-1]), flush=True)
     if "ditfp8" in which:  # whole-forward A/B of enable_fp8_ffn(), interleaved
         res.append(bench_dit(fp8_ab=True))
         print(json.dumps(res[-1]), flush=True)
@@ -285,6 +292,56 @@ def main(which=("gemm", "attn")):
         res.append(bench_dit(attn_variants=avars))
         print(json.dumps(res[-1]), flush=True)
     return res
+
+
+def _sclk_mhz():
+    """the graphics clock right now, or None where the runtime cannot tell"""
+    try:
+        return int(torch.cuda.clock_rate())
+    except Exception:  # noqa: BLE001
+        return None
+
+
+def bench_fp8_attn(L=21504, H=12, B=3):
+    """The config-2 self-attention launch (`kbench attn`'s: B = 3 rows of L = 21 504 tokens, 12 heads), same process,
+    interleaved rounds, median of 3: the bf16 auto kernel against K means + operand pack + MXFP8 flash kernel
+    (ops.attention_mxfp8), the flash kernel alone and the means + pack alone.  ratio = bf16 ms / fp8 ms (> 1: the fp8
+    path is faster); the graphics clock is read after each round."""
+    dev, D = "cuda", 128
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * L, 3 * H * D, device=dev, generator=g).bfloat16()
+    o = torch.empty(B * L, H * D, device=dev, dtype=torch.bfloat16)
+    o8 = torch.empty_like(o)
+    rows = [[b * L, L, b * L, L] for b in range(B)]
+    segs = torch.tensor(rows, dtype=torch.int32, device=dev)
+    vcol0, Rv = ops.attn_vcol0(rows)
+    vc = torch.tensor(vcol0, dtype=torch.int32, device=dev)
+    buf = ops.AttnMx8(B * L, B * L, H, Rv, B, dev)
+    q, k, v = qkv[:, :H * D], qkv[:, H * D:2 * H * D], qkv[:, 2 * H * D:]
+
+    def pack():
+        km = ops.attn_kmean(k, segs, B, H, buf.kmean, buf.kmean_work)
+        ops.attn_pack_mxfp8(q, k, v, segs, vc, B, L, L, H, buf, kmean=km)
+
+    fns = {"bf16": lambda: ops.attention(q, k, v, o, segs, B, L, H),
+           "fp8_total": lambda: ops.attention_mxfp8(q, k, v, o8, segs, B, L, H, vc, L, buf),
+           "fp8_kernel": lambda: ops.attn_fwd_mxfp8(buf, o8, segs, vc, B, L, H),
+           "fp8_pack": pack}
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(3):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=5, warmup=1))
+        clocks.append(_sclk_mhz())
+    ms = {n: sorted(t)[1] for n, t in times.items()}
+    fl = 4.0 * B * H * L * L * D
+    r = {"kernel": "fp8attn_self", "L": L, "heads": H, "rows": B, "sclk_mhz": clocks,
+         "rel_l2_fp8_vs_bf16": round(((o8.float() - o.float()).norm() / o.float().norm()).item(), 5)}
+    for n in fns:
+        r[f"{n}_ms"] = round(ms[n], 4)
+    r.update(ratio_total=round(ms["bf16"] / ms["fp8_total"], 3), ratio_kernel=round(ms["bf16"] / ms["fp8_kernel"], 3),
+             bf16_tflops=round(fl / ms["bf16"] / 1e9, 1), fp8_kernel_tflops=round(fl / ms["fp8_kernel"] / 1e9, 1))
+    print(json.dumps(r), flush=True)
+    return [r]
 
 
 def bench_fp8_ffn(M=3 * 21504, C=1536, FF=8960, rpb=21504):
@@ -431,11 +488,13 @@ def attn_clip_inputs(layers=(0, 15, 29)):
     return out
 
 
-def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False):
+def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False, fp8_attn_ab=False):
     """One full 30-layer DiT forward at config 2 (B=3 CFG, 21 latent frames at 64x64, L=21504).
     attn_variants: time the forward under each self-attention schedule, interleaved rounds.
     fp8_ab: the forward with enable_fp8_ffn() off and on (two models on the same weights), interleaved rounds,
-    and the rel-L2 between their outputs."""
+    and the rel-L2 between their outputs.  fp8_attn_ab: the same for enable_fp8_attention() off, on, and on together
+    with enable_fp8_ffn() (three models on the same weights), each output's rel-L2 against off, the graphics clock
+    after each round."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -476,6 +535,29 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
         for k in fwds:
             r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
         r["ratio"] = round(r["bf16_ms"] / r["fp8_ffn_ms"], 4)
+        return r
+    if fp8_attn_ab:
+        modes = {"off": m}
+        for k in ("fp8_attn", "fp8_attn_ffn"):
+            mm = WanTransformer3DFantasyModel(**cfg)
+            mm.load_state_dict(m.state_dict())
+            modes[k] = mm.to(dev)
+            modes[k].enable_fp8_attention()
+        modes["fp8_attn_ffn"].enable_fp8_ffn()
+        times, clocks, outs = {k: [] for k in modes}, [], {}
+        with torch.no_grad():
+            for _ in range(3):
+                for k, mm in modes.items():
+                    f = lambda mm=mm: mm.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)  # noqa: E731
+                    times[k].append(_time(f, iters=2, warmup=1))
+                    outs[k] = f().float()
+                clocks.append(_sclk_mhz())
+        r = {"kernel": "dit_forward_fp8_attn_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks}
+        for k in modes:
+            r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
+            if k != "off":
+                r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
+                r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os

@@ -271,6 +271,88 @@ def linear_mxfp8(x, weight, bias=None, epilogue=EPI_BF16, out=None, residual=Non
     return out
 
 
+KMEAN_SPLIT = 16  # sa_attn_kmean's row ranges per segment (its work buffer: nseg * KMEAN_SPLIT * heads * 128 floats)
+
+
+class AttnMx8:
+    """The operand buffers of attention_mxfp8 (stableavatar_amd/mxfp8_attn.py), allocated once by their owner: Q^ / K^
+    bytes [rows, heads * 128] + scales [rows, heads * 4], V^T bytes [heads * 128, Rv] + scales [heads * 128, Rv / 32],
+    k_mean fp32 [nseg, heads * 128] and sa_attn_kmean's partial sums."""
+
+    def __init__(self, q_rows, k_rows, heads, Rv, nseg, device):
+        C = heads * 128
+        if Rv <= 0 or Rv % 128:
+            raise ValueError(f"AttnMx8: Rv = {Rv} must be a positive multiple of 128")
+        u8 = dict(device=device, dtype=torch.uint8)
+        self.heads, self.Rv, self.nseg = heads, Rv, nseg
+        self.qq, self.qs = torch.empty(q_rows, C, **u8), torch.empty(q_rows, C // 32, **u8)
+        self.kq, self.ks = torch.empty(k_rows, C, **u8), torch.empty(k_rows, C // 32, **u8)
+        self.vq, self.vs = torch.empty(C, Rv, **u8), torch.empty(C, Rv // 32, **u8)
+        self.kmean = torch.empty(nseg, C, device=device, dtype=torch.float32)
+        self.kmean_work = torch.empty(nseg * KMEAN_SPLIT, C, device=device, dtype=torch.float32)
+
+
+def attn_vcol0(seg_rows):
+    """host side of the V^T layout for a list of {q_row0, q_len, kv_row0, kv_len}: ([vcol0 per segment], Rv), each
+    segment owning ceil128(kv_len) columns"""
+    from .mxfp8_attn import make_vcol0
+    return make_vcol0(seg_rows)
+
+
+def attn_kmean(k, segs, nseg, heads, out, work=None):
+    """out fp32 [nseg, heads * 128] = column means of bf16 k over each segment's keys (sa_attn_kmean); work: fp32
+    scratch of nseg * KMEAN_SPLIT * heads * 128 elements (allocated when None)"""
+    _check(k, torch.bfloat16, "attn_kmean.k")
+    assert k.stride(-1) == 1 and out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] >= nseg
+    if work is None:
+        work = torch.empty(nseg * KMEAN_SPLIT, heads * 128, device=k.device, dtype=torch.float32)
+    assert work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= nseg * KMEAN_SPLIT * heads * 128
+    call("sa_attn_kmean", k.data_ptr(), k.stride(0), segs.data_ptr(), nseg, heads, 128, out.data_ptr(),
+         work.data_ptr(), _stream())
+    return out
+
+
+def attn_pack_mxfp8(q, k, v, segs, vcol0, nseg, max_q_len, max_kv_len, heads, buf, scale=None, kmean=None):
+    """bf16 q, k, v rows -> the MXFP8 operands in `buf` (AttnMx8), bit for bit mxfp8_attn.pack (sa_attn_pack_mxfp8);
+    kmean: fp32 [nseg, heads * 128] subtracted from k, or None"""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _check(t, torch.bfloat16, f"attn_pack_mxfp8.{n}")
+        assert t.stride(-1) == 1
+    assert segs.dtype == torch.int32 and segs.is_cuda and vcol0.dtype == torch.int32 and vcol0.is_cuda
+    assert buf.heads == heads and buf.qq.shape[0] >= q.shape[0] and buf.kq.shape[0] >= k.shape[0]
+    if scale is None:
+        scale = 128 ** -0.5
+    call("sa_attn_pack_mxfp8", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+         segs.data_ptr(), vcol0.data_ptr(), nseg, max_q_len, max_kv_len, heads, 128, float(scale), _p(kmean),
+         buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(), buf.vq.data_ptr(),
+         buf.vs.data_ptr(), buf.Rv, _stream())
+    return buf
+
+
+def attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows=None):
+    """the flash kernel on packed operands (sa_attn_fwd_mxfp8); out bf16 [rows, >= heads * 128]"""
+    _check(out, torch.bfloat16, "attn_fwd_mxfp8.out")
+    assert out.stride(-1) == 1 and buf.heads == heads
+    if o_rows is not None:
+        assert o_rows.dtype == torch.int32 and o_rows.is_cuda and o_rows.is_contiguous()
+    call("sa_attn_fwd_mxfp8", buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(),
+         buf.vq.data_ptr(), buf.vs.data_ptr(), buf.Rv, out.data_ptr(), out.stride(0), segs.data_ptr(),
+         vcol0.data_ptr(), nseg, max_q_len, heads, 128, _p(o_rows), _stream())
+    return out
+
+
+def attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv_len, buf, head_dim=128, scale=None,
+                    o_rows=None, k_mean=True):
+    """Self-attention on MXFP8 operands (the fp8 attention mode; mxfp8_attn.py is the definition): the K column means
+    of each segment, the operand pack, the flash kernel.  q, k, v bf16 rows as attention(); vcol0: device int32 per
+    segment and max_kv_len from attn_vcol0's layout (buf.Rv its second result); buf: AttnMx8 owned by the caller."""
+    if head_dim != 128:
+        raise ValueError("attention_mxfp8: head_dim 128 only")
+    km = attn_kmean(k, segs, nseg, heads, buf.kmean, buf.kmean_work) if k_mean else None
+    attn_pack_mxfp8(q, k, v, segs, vcol0, nseg, max_q_len, max_kv_len, heads, buf, scale, km)
+    return attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows)
+
+
 def qk_rmsnorm_rope(x, q_col, k_col, wq, wk, C, eps, rope=None, rows_per_batch=0, tok_offset=0, grid=(1, 1, 1),
                     head_dim=128, n_frame_pairs=0, n_height_pairs=0, M=None):
     M = x.shape[0] if M is None else M

@@ -181,13 +181,28 @@ class _Seg:
 
     def __init__(self):
         self._c = {}
+        self._rows = {}  # id(table) -> its host rows (the tables live as long as the cache)
+        self._vt = {}  # id(table) -> (vcol0 device int32, Rv, max kv_len): the fp8 attention's V^T layout
 
     def get(self, key, rows, device):
         t = self._c.get(key)
         if t is None or t.device != device:
             t = torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(device)
             self._c[key] = t
+            self._rows[id(t)] = [list(r) for r in torch.tensor(rows).reshape(-1, 4).tolist()]
+            self._vt.pop(id(t), None)
         return t
+
+    def vt_layout(self, table):
+        """(vcol0, Rv, max kv_len) of a table this cache handed out: each segment's first V^T column (host-computed,
+        multiples of 128) for ops.attention_mxfp8"""
+        lay = self._vt.get(id(table))
+        if lay is None:
+            rows = self._rows[id(table)]
+            vcol0, Rv = ops.attn_vcol0(rows)
+            lay = (torch.tensor(vcol0, dtype=torch.int32).to(table.device), Rv, max(r[3] for r in rows))
+            self._vt[id(table)] = lay
+        return lay
 
 
 class WanTransformer3DFantasyModel(nn.Module):
@@ -226,6 +241,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         self._riflex = None  # enable_riflex() (1B:890-905)
         self.attn_kernel = 0  # self-attention schedule (sa_attn_fwd_ex; 0 = auto), for in-situ A/B
         self._fp8_ffn = False  # enable_fp8_ffn(): the blocks' FFN GEMMs on MXFP8 operands
+        self._fp8_attn = False  # enable_fp8_attention(): the blocks' self-attention on MXFP8 operands
         self._packed = None
         self._ws = {}
         self._ctx_cache = None
@@ -331,6 +347,34 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._fp8_ffn = enabled
             self._packed = None
             self._ws = {}
+
+    def enable_fp8_attention(self, enabled=True):
+        """MI355X addition (no counterpart in the reference; changes numerics): the self-attention of every DiT block
+        (1B:383-413) runs both its products, Q K^T and P V, on MXFP8 operands (stableavatar_amd/mxfp8_attn.py is the
+        definition; block-scaled e4m3 MFMA, fp32 softmax and accumulation).  Cross-attention, the vocal projector's
+        attention and every GEMM are untouched; combines with enable_fp8_ffn().  Off, the calls made are the bf16
+        path's.  Toggling drops the workspace (the operand buffers live there); the packed weights stay."""
+        enabled = bool(enabled)
+        if enabled and self.d != 128:
+            raise ValueError(f"enable_fp8_attention: head_dim {self.d} != 128")
+        if enabled != self._fp8_attn:
+            self._fp8_attn = enabled
+            self._ws = {}
+
+    def _self_attn(self, ws, q, k, v, out, segs, nseg, max_q_len, heads, kernel=0, o_rows=None, split_tiles=0):
+        """One self-attention launch of a DiT block: ops.attention, or with enable_fp8_attention() the K means, the
+        operand pack and the MXFP8 flash kernel (ops.attention_mxfp8; no key split there).  The operand buffers live
+        in the workspace, one set per segment table (the per-row streams of the sequence-parallel schedule run
+        concurrently, each on its own table), allocated on first use."""
+        if not self._fp8_attn:
+            return ops.attention(q, k, v, out, segs, nseg, max_q_len, heads, kernel=kernel, o_rows=o_rows,
+                                 split_tiles=split_tiles)
+        vcol0, Rv, max_kv = self._segs.vt_layout(segs)
+        key = (id(segs), q.shape[0], k.shape[0], heads)
+        buf = ws.attn8.get(key)
+        if buf is None:
+            buf = ws.attn8[key] = ops.AttnMx8(q.shape[0], k.shape[0], heads, Rv, nseg, q.device)
+        return ops.attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv, buf, o_rows=o_rows)
 
     def enable_multi_gpus_inference(self, group=None, loopback=None):
         """Ulysses sequence parallelism over torch.distributed (RCCL); replaces the xfuser path
@@ -464,6 +508,7 @@ class WanTransformer3DFantasyModel(nn.Module):
                 att=torch.empty(M, dim, device=dev, dtype=torch.bfloat16),
                 ffn=torch.empty(M, self.ffn_dim, device=dev, dtype=torch.bfloat16) if not self._fp8_ffn else None,
                 vt=None,  # V^T [dim, M rounded up to 64] of the single-GPU self-attention, allocated on first use
+                attn8={},  # enable_fp8_attention(): ops.AttnMx8 operand buffers per segment table (_self_attn)
             )
             if self._fp8_ffn:  # the FFN's operands as MXFP8: its LayerNorm output and its hidden activations
                 ws.modq = ops.Mx8.empty(M, dim, dev)
@@ -653,8 +698,8 @@ class WanTransformer3DFantasyModel(nn.Module):
             with torch.cuda.stream(st):
                 pend[b].wait()
                 ev0 = self._record_event()
-                ops.attention(ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq, hg,
-                              kernel=akern, o_rows=ex.omap, split_tiles=splits[b])
+                self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq, hg,
+                                kernel=akern, o_rows=ex.omap, split_tiles=splits[b])
                 self._record_span(ev0, rows=1, batch=B)
                 back.append(ex.tokens([b]))
         for b, st in enumerate(rstreams):  # O-projection + gated residual, cross-attention, FFN (1B:677-691)
@@ -712,8 +757,8 @@ class WanTransformer3DFantasyModel(nn.Module):
         ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, eps, b_offset=0, **pack_kw, **rope_kw)
         ex.heads([0]).wait()
         ev0 = self._record_event()
-        ops.attention(ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, seg0, 1, Lq, hg, kernel=self.attn_kernel,
-                      o_rows=ex.omap)
+        self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, seg0, 1, Lq, hg, kernel=self.attn_kernel,
+                        o_rows=ex.omap)
         self._record_span(ev0, rows=1, batch=B)
         ex.tokens([0]).wait()
         a0, pnl = ex.panels(range(0, 1))
@@ -743,8 +788,8 @@ class WanTransformer3DFantasyModel(nn.Module):
             ops.linear(mod, L.w_qkv, L.b_qkv, ops.EPI_BF16, out=qkv)
             ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **rope_kw)
             ev0 = self._record_event()
-            ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs, nb, Lp, H_,
-                          kernel=self.attn_kernel)
+            self._self_attn(ws, qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs, nb, Lp, H_,
+                            kernel=self.attn_kernel)
         self._record_span(ev0, rows=nb, batch=batch)
         ops.linear(att, L.w_o, L.b_o, ops.EPI_RES_F32, out=xr, residual=xr, gate=em[:nb, 2], rows_per_batch=Lc)
 
@@ -938,7 +983,7 @@ class WanTransformer3DFantasyModel(nn.Module):
             use_cross3 = (ctx.img_len > 0 and G % 256 == 0 and (rank * Lc) % 256 == 0 and (rank + 1) * Lc <= S
                           and os.environ.get("SA_CROSS3", "1") != "0")
             x = ws.x
-            use_vt = not SP and self._vt_attention(Lp, dev)
+            use_vt = not SP and not self._fp8_attn and self._vt_attention(Lp, dev)
             # shared_rows: the first block's self-attention half once (single-GPU layout, or the one-stream and
             # per-row-stream Ulysses schedules)
             dedup = shared_rows and broadcast and B > 1 and (not SP or sp_streams or not (sp_rows or sp_rows_x))
@@ -1006,8 +1051,8 @@ class WanTransformer3DFantasyModel(nn.Module):
                         for b in range(B):
                             pend[b].wait()
                             ev0 = self._record_event()
-                            ops.attention(ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq, hg,
-                                          kernel=self.attn_kernel, o_rows=ex.omap)
+                            self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq,
+                                            hg, kernel=self.attn_kernel, o_rows=ex.omap)
                             self._record_span(ev0, rows=1, batch=B)
                             back.append(ex.tokens([b]))
                         for b in range(B):
@@ -1036,8 +1081,8 @@ class WanTransformer3DFantasyModel(nn.Module):
                         # to the owners' send slabs / this rank's own O-projection panel, then heads -> tokens
                         ev0 = self._record_event()
                         split = ops.attn_tail_split(0, B * hg * -(-Lq // 256), dev) if self.attn_kernel == 0 else 0
-                        ops.attention(ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_self, B, Lq, hg,
-                                      kernel=self.attn_kernel, o_rows=ex.omap, split_tiles=split)
+                        self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_self, B, Lq, hg,
+                                        kernel=self.attn_kernel, o_rows=ex.omap, split_tiles=split)
                         self._record_span(ev0, rows=B, batch=B)
                         ex.tokens(range(B)).wait()
                         a0, pnl = ex.panels()
