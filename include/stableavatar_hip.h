@@ -205,6 +205,37 @@ int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void* k, const 
                       const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim, const int32_t* o_rows,
                       void* stream);
 
+/* ---- fp8 q/k/v mode feeding the fp8 attention directly (opt-in; no counterpart in the reference) ----
+ * Three entry points that write the operands of sa_attn_fwd_mxfp8 where their values are made.  Each is bit-identical
+ * to the pair of calls it replaces, and checks every argument before its first HIP call. */
+
+/* The V projection whose epilogue writes V^T: sa_gemm_mxfp8's K loop (same fp32 accumulators, operand rules and
+ * alignment: K % 128 == 0, lda/ldw % 16 == 0, 16-B aligned operands, dword scale rows) on A [M][K], W [N][K],
+ * N % 128 == 0, M = nseg * rows_per_seg.  Segment s is rows s * rows_per_seg ..; it owns V^T columns
+ * s * ceil128(rows_per_seg) .. + ceil128(rows_per_seg) (mxfp8_attn.make_vcol0 for equal segments) of
+ * vt_out [N][Rv] bytes / vt_scales [N][Rv / 32]; Rv % 128 == 0, Rv >= nseg * ceil128(rows_per_seg), vt_out 16-B
+ * aligned.  The result is what sa_gemm_mxfp8(SA_EPI_BF16) into a bf16 [M][N] followed by the V^T third of
+ * sa_attn_pack_mxfp8 writes: keys in the P^T operand's position order, 32-position blocks, keys at or past
+ * rows_per_seg zero bytes (an all-zero block has scale byte 127).  rows_per_seg need not be a multiple of 128. */
+int sa_gemm_mxfp8_vt(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                     const void* W_scales, int64_t ldws, const float* bias, void* vt_out, void* vt_scales, int64_t Rv,
+                     int M, int N, int K, int rows_per_seg, int nseg, void* stream);
+
+/* sa_qk_rmsnorm_rope (below; same arguments and kernel choice) that emits the Q operand: k is normalised, rotated and
+ * stored in place as bf16, byte for byte as sa_qk_rmsnorm_rope does; q is NOT stored back -- its normalised, rotated
+ * values, rounded to bf16, leave as q_out [M][ldq] = quant(fp32(q) * (scale * log2 e)) along D with
+ * q_scales [M][ldqs], for every one of the M rows: sa_qk_rmsnorm_rope followed by the Q third of
+ * sa_attn_pack_mxfp8.  head_dim 128 only, C % 128 == 0, ldq % 8 == 0, q_out 8-B and x 16-B aligned. */
+int sa_qk_rmsnorm_rope_mxfp8(void* x, int64_t ldx, int q_col, int k_col, const float* wq, const float* wk, int M,
+                             int C, int head_dim, float eps, const float* rope, int rows_per_batch, int tok_offset,
+                             int F, int H, int W, int n_frame_pairs, int n_height_pairs, void* q_out, int64_t ldq,
+                             void* q_scales, int64_t ldqs, float scale, void* stream);
+
+/* The K third of sa_attn_pack_mxfp8 alone (same kernel, same bytes): k_out / k_scales = quant(fp32(k) -
+ * k_mean[seg][column]) over each segment's key rows (k_mean NULL: no subtraction).  head_dim is 128. */
+int sa_attn_pack_k_mxfp8(const void* k, int64_t k_stride, const int32_t* segs, int nseg, int max_kv_len, int heads,
+                         const float* k_mean, void* k_out, void* k_scales, void* stream);
+
 /* WanRMSNorm over the full width on q (and k) + rope_apply (1B:295-342, :395-396, :403-404) in place.
  * rope = fp32 [1024][head_dim/2][2] (cos, sin) table or NULL (no rotation); token index
  * t = tok_offset + row % rows_per_batch; t >= F*H*W is not rotated (padding, 1B:319). */

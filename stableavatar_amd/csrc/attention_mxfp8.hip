@@ -2,7 +2,8 @@
 // stableavatar_amd/mxfp8_attn.py is the definition: Q^ = quant(q * scale * log2 e) and K^ = quant(k - k_mean) along D,
 // V^T quantised along the keys in the P^T operand's position order, P^ = e4m3(exp2(s - m) * 2^P_SHIFT),
 // o = (P^ V^) / sum(P^).  Three kernels: sa_attn_kmean (column means of K per segment), sa_attn_pack_mxfp8 (the three
-// operands, bit for bit the definition's) and sa_attn_fwd_mxfp8, the flash loop on
+// operands, bit for bit the definition's; sa_attn_pack_k_mxfp8 is its K third alone, for the fp8 q/k/v mode whose
+// GEMM and RoPE kernels write V^T and Q^ themselves) and sa_attn_fwd_mxfp8, the flash loop on
 // v_mfma_scale_f32_16x16x128_f8f6f4 (lane map: gemm_mxfp8.hip).
 //
 // sa_attn_fwd_mxfp8: 8 waves x 32 queries as attention.hip's kernels, 128-key blocks.  S^T = K^ Q^T: one scaled MFMA
@@ -346,12 +347,13 @@ struct PackArgs {
   uint8_t* vq; uint8_t* vsc;
   long Rv;
   int heads;
+  int only_k;  // sa_attn_pack_k_mxfp8: the grid has no query half
 };
 
 // Q^ and K^: one wave per row, 8 elements per lane per 512-column chunk, a block is four adjacent lanes (as
-// mxfp8_quant_kernel); blockIdx.z = 0 the segment's query rows, 1 its key rows
+// mxfp8_quant_kernel); blockIdx.z = 0 the segment's query rows, 1 its key rows (only_k: the key rows alone)
 __global__ __launch_bounds__(256) void attn_pack_qk_kernel(PackArgs a) {
-  const int seg = blockIdx.y, isk = blockIdx.z;
+  const int seg = blockIdx.y, isk = a.only_k ? 1 : blockIdx.z;
   const int* sg = a.segs + seg * 4;
   const int row0 = sg[isk ? 2 : 0], len = sg[isk ? 3 : 1];
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -464,7 +466,7 @@ extern "C" int sa_attn_pack_mxfp8(const void* q, int64_t q_stride, const void* k
   if (k_mean && (((uintptr_t)k_mean) & 3)) return SA_ERR_ARG;
   PackArgs a{(const bf16*)q, q_stride, (const bf16*)k, k_stride, (const bf16*)v, v_stride, segs, vcol0, k_mean,
              scale * 1.4426950408889634f, (uint8_t*)q_out, (uint8_t*)q_scales, (uint8_t*)k_out, (uint8_t*)k_scales,
-             (uint8_t*)vt_out, (uint8_t*)vt_scales, Rv, heads};
+             (uint8_t*)vt_out, (uint8_t*)vt_scales, Rv, heads, 0};
   hipStream_t st = (hipStream_t)stream;
   const int rows = max_q_len > max_kv_len ? max_q_len : max_kv_len;
   if (rows > 0) {
@@ -473,6 +475,21 @@ extern "C" int sa_attn_pack_mxfp8(const void* q, int64_t q_stride, const void* k
   }
   if (max_kv_len > 0) {
     hipLaunchKernelGGL(attn_pack_vt_kernel, dim3((max_kv_len + KVB - 1) / KVB, heads, nseg), dim3(256), 0, st, a);
+    SA_LAUNCH_CHECK();
+  }
+  return SA_OK;
+}
+
+extern "C" int sa_attn_pack_k_mxfp8(const void* k, int64_t k_stride, const int32_t* segs, int nseg, int max_kv_len,
+                                    int heads, const float* k_mean, void* k_out, void* k_scales, void* stream) {
+  if (!k || !segs || !k_out || !k_scales || nseg <= 0 || heads <= 0 || max_kv_len < 0) return SA_ERR_ARG;
+  const int64_t C = (int64_t)heads * D;
+  if (k_stride < C || k_stride % 8 || (((uintptr_t)k) & 15) || (((uintptr_t)k_out) & 15)) return SA_ERR_ARG;
+  if (k_mean && (((uintptr_t)k_mean) & 3)) return SA_ERR_ARG;
+  PackArgs a{nullptr, 0, (const bf16*)k, k_stride, nullptr, 0, segs, nullptr, k_mean, 0.f, nullptr, nullptr,
+             (uint8_t*)k_out, (uint8_t*)k_scales, nullptr, nullptr, 0, heads, 1};
+  if (max_kv_len > 0) {
+    hipLaunchKernelGGL(attn_pack_qk_kernel, dim3((max_kv_len + 3) / 4, nseg, 1), dim3(256), 0, (hipStream_t)stream, a);
     SA_LAUNCH_CHECK();
   }
   return SA_OK;

@@ -1,4 +1,5 @@
-// MXFP8 "NT" GEMM for the DiT's FFN Linears (opt-in fp8 FFN mode; the default path stays on gemm.hip):
+// MXFP8 "NT" GEMM for the DiT's FFN Linears (opt-in fp8 FFN mode) and its self-attention q/k/v Linears (opt-in fp8
+// q/k/v mode); the default path stays on gemm.hip:
 //   C[M,N] = epi(deq(A)[M,K] · deq(W)[N,K]^T + bias)
 // A and W are e4m3fn bytes, K-contiguous, with one E8M0 scale byte per 32 consecutive K elements
 // (stableavatar_amd/mxfp8.py is the definition); accumulation is fp32 on
@@ -14,6 +15,16 @@
 // four (the 16-byte chunks g and 4 + g of the row -- the bf16 kernels' fragment addresses), and byte 0 of its scale
 // operand is the E8M0 scale of K block g (bytes 32 g .. 32 g + 31) of row r.  Operands are swapped (C^T = W·A^T) so
 // each lane holds 4 consecutive output columns of one row.
+//
+// sa_gemm_mxfp8_vt (the V projection of the fp8 q/k/v mode, feeding sa_attn_fwd_mxfp8): the same K loop with the
+// operands NOT swapped (C = A·W^T; the product of two operand rows does not depend on which side they sit, so the
+// accumulators hold the same fp32 values as sa_gemm_mxfp8's), which leaves lane l = (column c = l % 16, group
+// g = l / 16) of tile (m, n) holding acc[m][n][e] = token row 16 m + 4 g + e of the wave's 128-row half, output column
+// 16 n + c.  The half is one 128-key block of one segment (the M axis is tiled per segment), m = 4 hi + t, and
+// mxfp8_attn.KEY_OF_POS puts key 16 (4 hi + t) + 4 g + e at position 64 hi + 16 g + 4 t + e of the block: for each hi
+// the lane's 16 values (t, e) are the 16 consecutive positions 64 hi + 16 g .. + 15 of V^T row (column) 16 n + c --
+// one 16-byte store -- and the 32-position quantisation block 2 hi + g / 2 is this lane's 16 values and those of the
+// lane 16 further (g ^ 1): one shfl_xor for its amax.
 // Also here: sa_mxfp8_quant, the bf16 -> MXFP8 quantiser (weights at pack time; the definition's GPU twin).
 #include <utility>
 
@@ -22,6 +33,7 @@
 namespace {
 
 enum { EPI_BF16 = 0, EPI_GELU_BF16 = 1, EPI_F32 = 2, EPI_RES_F32 = 3, EPI_GELU_MXFP8 = 8 };
+constexpr int EPI_VT = 100;  // sa_gemm_mxfp8_vt's kernel (not an epilogue code of the ABI)
 
 typedef int __attribute__((ext_vector_type(8))) i32x8;
 
@@ -35,6 +47,7 @@ struct MxArgs {
   int rows_per_batch;
   int M, N, K;
   int group_m;
+  int rows_per_seg, seg_mt;  // EPI_VT: rows of a segment, 256-row tiles per segment (C = V^T bytes, ldc = Rv)
 };
 
 constexpr int BM = 256, BN = 256, BKB = 128;  // BKB: K-tile bytes = fp8 elements
@@ -92,11 +105,16 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fc = lane >> 4;
-  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
+  constexpr bool VT = EPI == EPI_VT;
+  const int nm = VT ? (g.M / g.rows_per_seg) * g.seg_mt : (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
   const int wg = xcd_remap(blockIdx.x, nm * nn);
   int mt, nt;
   tile_coords(wg, nm, nn, g.group_m, mt, nt);
-  const int m0 = mt * BM, n0 = nt * BN;
+  // EPI_VT tiles the M axis per segment: tile mt is rows t0 .. t0 + 255 of segment sg (rows at or past rows_per_seg
+  // are clamped to the segment's last row on load and written as zeros)
+  const int sg = VT ? mt / g.seg_mt : 0, t0 = VT ? (mt % g.seg_mt) * BM : 0;
+  const int m0 = VT ? sg * g.rows_per_seg + t0 : mt * BM, n0 = nt * BN;
+  const int m_last = VT ? (sg + 1) * g.rows_per_seg - 1 : g.M - 1;  // the last row a load of this tile may touch
   const int nk = g.K / BKB;
 
   // staging: half-tile h (0, 1 = A rows 0-127 / 128-255, 2, 3 = W) is 16 pieces of 1 KB (8 rows), four per wave;
@@ -110,7 +128,7 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
       const int row = (i * 4 + wave) * 8 + (lane >> 3);
       const int chunk = (lane & 7) ^ ((row >> 1) & 7);
       if (h < 2)
-        goff[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
+        goff[h][i] = min(m0 + h * 128 + row, m_last) * (int)g.lda + chunk * 16;
       else
         goff[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
     }
@@ -125,7 +143,7 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
   };
   // the K-tile's scale bytes ride along: one dword (the tile's four K blocks) per row, thread i fetching row i of
   // the A and of the W tile into [256] dwords each behind the ring
-  const int soff_a = min(m0 + tid, g.M - 1) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+  const int soff_a = min(m0 + tid, m_last) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
   auto issue_scales = [&](int kt) {
     char* dst = smem + LDS_BYTES + (kt & 1) * SCALE_STAGE + wave * 256;
     __builtin_amdgcn_global_load_lds((const void*)(g.SA + soff_a + kt * 4), LDS_PTR(dst), 4, 0, 0);
@@ -196,12 +214,50 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
       }
       const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
 #pragma unroll
-      for (int n = 0; n < 8; ++n) mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
+      for (int n = 0; n < 8; ++n) {
+        if constexpr (VT)
+          mx_mma(acc[m][n], a, b[n], sa[m], sw[n]);
+        else
+          mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
+      }
     });
   }
 
   // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+
+  if constexpr (VT) {
+    // V^T epilogue (lane map: the header): this wave's half is keys k0 .. k0 + 127 of segment sg, V^T columns
+    // vc .. vc + 127; a half that starts at or past the segment's end owns no columns and writes nothing
+    const int k0 = t0 + wm * 128, cw = n0 + wn * 128;
+    if (k0 >= g.rows_per_seg || cw >= g.N) return;
+    const long vc = (long)sg * ((g.rows_per_seg + 127) / 128 * 128) + k0;
+    uint8_t* Vq = (uint8_t*)g.C;
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+      const int col = cw + n * 16 + fr;
+      const float bv = g.bias ? g.bias[col] : 0.f;
+#pragma unroll
+      for (int hi = 0; hi < 2; ++hi) {
+        float v[16];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            // the bf16 rounding of the Linear output (SA_EPI_BF16), keys past the segment as zeros
+            const bool live = k0 + 16 * (4 * hi + t) + 4 * fc + e < g.rows_per_seg;
+            v[4 * t + e] = live ? bf2f(f2bf(acc[4 * hi + t][n][e] + bv)) : 0.f;
+          }
+        float amax = fmaxf(mx_amax8(v), mx_amax8(v + 8));
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        uint32_t s;
+        const u32x2 lo = mx_quant8(v, amax, &s), hi2 = mx_quant8(v + 8, amax, &s);
+        *(u32x4*)(Vq + (long)col * g.ldc + vc + 64 * hi + 16 * fc) = (u32x4){lo[0], lo[1], hi2[0], hi2[1]};
+        if ((fc & 1) == 0) g.SC[(long)col * g.ldsc + vc / 32 + 2 * hi + (fc >> 1)] = (uint8_t)s;
+      }
+    }
+    return;
+  }
 
   // epilogue straight from the accumulators: acc[m][n] of lane (fr, fc) = row m0 + wm*128 + m*16 + fr, columns
   // n0 + wn*128 + n*16 + 4 fc + 0..3.  Walked in column pairs (n = 2p, 2p + 1): the 32 columns of pair p in one row
@@ -303,7 +359,7 @@ int launch(const MxArgs& g, hipStream_t st) {
     return true;
   }();
   (void)attr;
-  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
+  const int nm = EPI == EPI_VT ? (g.M / g.rows_per_seg) * g.seg_mt : (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
   hipLaunchKernelGGL((gemm_mx_kernel<EPI>), dim3(nm * nn), dim3(256), LDS_TOTAL, st, g);
   SA_LAUNCH_CHECK();
   return SA_OK;
@@ -371,7 +427,7 @@ extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, i
   if (epilogue == EPI_GELU_MXFP8 && (N % 32 != 0 || !C_scales || ldcs < N / 32)) return SA_ERR_ARG;
   MxArgs g{(const uint8_t*)A, lda, (const uint8_t*)A_scales, ldas, (const uint8_t*)W, ldw, (const uint8_t*)W_scales, ldws,
            bias, C, ldc, (uint8_t*)C_scales, ldcs, residual, ldr, gate, gate_bstride,
-           rows_per_batch > 0 ? rows_per_batch : 1, M, N, K, epilogue == EPI_RES_F32 ? 4 : 8};
+           rows_per_batch > 0 ? rows_per_batch : 1, M, N, K, epilogue == EPI_RES_F32 ? 4 : 8, M, 0};
   hipStream_t st = (hipStream_t)stream;
   switch (epilogue) {
     case EPI_BF16: return launch<EPI_BF16>(g, st);
@@ -381,4 +437,27 @@ extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, i
     case EPI_GELU_MXFP8: return launch<EPI_GELU_MXFP8>(g, st);
     default: return SA_ERR_ARG;
   }
+}
+
+extern "C" int sa_gemm_mxfp8_vt(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,
+                                int64_t ldw, const void* W_scales, int64_t ldws, const float* bias, void* vt_out,
+                                void* vt_scales, int64_t Rv, int M, int N, int K, int rows_per_seg, int nseg,
+                                void* stream) {
+  if (!A || !A_scales || !W || !W_scales || !vt_out || !vt_scales || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
+  if (rows_per_seg <= 0 || nseg <= 0 || (long)nseg * rows_per_seg != M) return SA_ERR_ARG;
+  if (K % BKB != 0 || N % 128 != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 ||
+      ldws < K / 32)
+    return SA_ERR_ARG;
+  if ((((uintptr_t)A) & 15) || (((uintptr_t)W) & 15)) return SA_ERR_ARG;
+  if (ldas % 4 != 0 || ldws % 4 != 0 || (((uintptr_t)A_scales) & 3) || (((uintptr_t)W_scales) & 3)) return SA_ERR_ARG;
+  if ((long)M * lda >= 0x7fffffffL || (long)N * ldw >= 0x7fffffffL || (long)M * ldas >= 0x7fffffffL ||
+      (long)N * ldws >= 0x7fffffffL)
+    return SA_ERR_ARG;
+  // every segment owns ceil128(rows_per_seg) columns of the Rv; 16-byte stores into vt_out
+  const long seg_cols = ((long)rows_per_seg + 127) / 128 * 128;
+  if (Rv <= 0 || Rv % 128 != 0 || Rv < nseg * seg_cols || (((uintptr_t)vt_out) & 15)) return SA_ERR_ARG;
+  MxArgs g{(const uint8_t*)A, lda, (const uint8_t*)A_scales, ldas, (const uint8_t*)W, ldw, (const uint8_t*)W_scales, ldws,
+           bias, vt_out, Rv, (uint8_t*)vt_scales, Rv / 32, nullptr, 0, nullptr, 0, 1, M, N, K, 8, rows_per_seg,
+           (rows_per_seg + BM - 1) / BM};
+  return launch<EPI_VT>(g, (hipStream_t)stream);
 }

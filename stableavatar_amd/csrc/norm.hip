@@ -6,6 +6,9 @@
 //  * sa_qk_rmsnorm_rope: WanRMSNorm over the FULL model dim on q and k (1B:326-342,395-396),
 //    then the 3-D complex RoPE (1B:295-323) with fp64-derived fp32 (cos,sin) tables; tokens past
 //    f*h*w (padding) are left unrotated (1B:319).  In place on the fused QKV GEMM output.
+//  * sa_qk_rmsnorm_rope_mxfp8 (fp8 q/k/v mode with fp8 attention): the same kernels with another store for q -- k goes
+//    back in place, q's normalised, rotated values are rounded to bf16 and leave as the attention's MXFP8 Q operand
+//    (= sa_qk_rmsnorm_rope followed by the Q third of sa_attn_pack_mxfp8)
 #include "mxfp8.h"
 #include <cstdlib>
 
@@ -153,6 +156,32 @@ struct QkArgs {
 struct StoreInPlace {
   bf16* p;
   __device__ __forceinline__ void operator()(int c0, const float* y) const { store8<bf16>(p + c0, y); }
+};
+
+// the Q operand of the fp8 attention from one normalised, rotated 8-column chunk: the values as bf16 would hold them,
+// times c = scale * log2 e, quantised along D; a 32-column block is four adjacent lanes (C % 32 == 0: active together)
+struct StoreQuantQ {
+  uint8_t* q; uint8_t* s;  // this row's element bytes and scale bytes
+  float c;
+  __device__ __forceinline__ void operator()(int c0, const float* y) const {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(y[j])) * c;
+    float amax = mx_amax8(v);
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    uint32_t sb;
+    const u32x2 w = mx_quant8(v, amax, &sb);
+    *(u32x2*)(q + c0) = w;
+    if ((c0 & 31) == 0) s[c0 / 32] = (uint8_t)sb;
+  }
+};
+
+struct QkMxArgs {
+  QkArgs qk;
+  uint8_t* qo; long ldq;
+  uint8_t* qs; long ldqs;
+  float c;
 };
 
 template <int FIXED, class Store>
@@ -303,6 +332,42 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_rope_pair_kernel(QkArgs a) {
   bf16* kp = a.x + (long)row * a.ldx + a.k_col + lane * 8;
   qk_pair_row(a, row, lane, [&](int i, const float* yq, const float* yk) {
     store8<bf16>(qp + i * 512, yq);
+    store8<bf16>(kp + i * 512, yk);
+  });
+}
+
+template <int FIXED = 0>
+__global__ __launch_bounds__(256) void qk_rmsnorm_rope_mx_kernel(QkMxArgs m) {
+  const QkArgs& a = m.qk;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= a.M) return;
+  bool rot = false;
+  int fi = 0, hi_ = 0, wi = 0;
+  if (a.rope) {
+    const int t = a.tok_offset + row % a.rows_per_batch;
+    if (t < a.F * a.H * a.W) {
+      rot = true;
+      fi = t / (a.H * a.W);
+      hi_ = (t / a.W) % a.H;
+      wi = t % a.W;
+    }
+  }
+  bf16* base = a.x + (long)row * a.ldx;
+  rms_rope_one<FIXED>(base + a.q_col, a.wq, a, lane, fi, hi_, wi, rot,
+                      StoreQuantQ{m.qo + (long)row * m.ldq, m.qs + (long)row * m.ldqs, m.c});
+  if (a.k_col >= 0) rms_rope_one<FIXED>(base + a.k_col, a.wk, a, lane, fi, hi_, wi, rot, StoreInPlace{base + a.k_col});
+}
+
+__global__ __launch_bounds__(256) void qk_rmsnorm_rope_pair_mx_kernel(QkMxArgs m) {
+  const QkArgs& a = m.qk;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= a.M) return;
+  bf16* kp = a.x + (long)row * a.ldx + a.k_col + lane * 8;
+  const StoreQuantQ sq{m.qo + (long)row * m.ldq, m.qs + (long)row * m.ldqs, m.c};
+  qk_pair_row(a, row, lane, [&](int i, const float* yq, const float* yk) {
+    sq(i * 512 + lane * 8, yq);
     store8<bf16>(kp + i * 512, yk);
   });
 }
@@ -544,6 +609,34 @@ extern "C" int sa_qk_rmsnorm_rope(void* x, int64_t ldx, int q_col, int k_col, co
     hipLaunchKernelGGL(qk_rmsnorm_rope_kernel<10>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(qk_rmsnorm_rope_kernel<0>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+extern "C" int sa_qk_rmsnorm_rope_mxfp8(void* x, int64_t ldx, int q_col, int k_col, const float* wq, const float* wk,
+                                        int M, int C, int head_dim, float eps, const float* rope, int rows_per_batch,
+                                        int tok_offset, int F, int H, int W, int n_frame_pairs, int n_height_pairs,
+                                        void* q_out, int64_t ldq, void* q_scales, int64_t ldqs, float scale,
+                                        void* stream) {
+  if (!x || !wq || !q_out || !q_scales || M <= 0 || C <= 0 || C > 512 * MAXV || ldx % 8) return SA_ERR_ARG;
+  if (head_dim != 128 || C % 128 || q_col < 0) return SA_ERR_ARG;
+  if (k_col >= 0 && !wk) return SA_ERR_ARG;
+  if (rope && (rows_per_batch <= 0 || F <= 0 || H <= 0 || W <= 0)) return SA_ERR_ARG;
+  if (ldq < C || ldq % 8 || ldqs < C / 32 || (((uintptr_t)q_out) & 7) || (((uintptr_t)x) & 15)) return SA_ERR_ARG;
+  QkMxArgs m{QkArgs{(bf16*)x, ldx, q_col, k_col, wq, wk, M, C, head_dim, eps, rope,
+                    rows_per_batch > 0 ? rows_per_batch : 1, tok_offset, F, H, W, n_frame_pairs, n_height_pairs},
+             (uint8_t*)q_out, ldq, (uint8_t*)q_scales, ldqs, scale * 1.4426950408889634f};
+  // the kernel choice is sa_qk_rmsnorm_rope's, so that the values quantised are the ones it would have stored
+  static const bool generic = getenv("SA_QK_GENERIC") != nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (rope && k_col >= 0 && C == 1536 && !generic)
+    hipLaunchKernelGGL(qk_rmsnorm_rope_pair_mx_kernel, dim3((M + 3) / 4), dim3(256), 0, st, m);
+  else if (C == 1536)
+    hipLaunchKernelGGL(qk_rmsnorm_rope_mx_kernel<3>, dim3((M + 3) / 4), dim3(256), 0, st, m);
+  else if (C == 5120)
+    hipLaunchKernelGGL(qk_rmsnorm_rope_mx_kernel<10>, dim3((M + 3) / 4), dim3(256), 0, st, m);
+  else
+    hipLaunchKernelGGL(qk_rmsnorm_rope_mx_kernel<0>, dim3((M + 3) / 4), dim3(256), 0, st, m);
   SA_LAUNCH_CHECK();
   return SA_OK;
 }

@@ -21,6 +21,9 @@ Flag mapping:
   MXFP8 operands (DESIGN.md "fp8 FFN"); changes numerics; combines with every flag above;
 * ``--fp8_attn`` (no counterpart in the reference): ``transformer.enable_fp8_attention()``, the DiT blocks'
   self-attention on MXFP8 operands (DESIGN.md "fp8 attention"); changes numerics; combines with every flag above;
+* ``--fp8_qkv`` (no counterpart in the reference): ``transformer.enable_fp8_qkv()``, the q/k/v Linears of the DiT
+  blocks' self-attention on MXFP8 operands (DESIGN.md "fp8 q/k/v"); with ``--fp8_attn`` the attention operands are
+  written by the V GEMM and the RoPE kernel themselves; changes numerics; combines with every flag above;
 * ``--fsdp_dit`` / ``--t5_fsdp`` / ``--t5_cpu`` / ``--offload_model``: accepted, no effect (the 3.5 GB DiT is
   replicated).
 Audio is read with scipy (16-bit / float WAV, channels averaged, polyphase resampling to 16 kHz) where the
@@ -94,6 +97,15 @@ def parse_args(argv=None):
                         "times as sharp; real checkpoints unmeasured) and has no counterpart in the reference. "
                         "Measured: the self-attention launch 1.38x with its operand pack included, the 30-layer "
                         "forward 1.10x, 1.25x together with --fp8_ffn (DESIGN.md, fp8 attention).")
+    p.add_argument("--fp8_qkv", action="store_true",
+                   help="run the q, k and v Linears of the DiT blocks' self-attention on MXFP8 operands (block-scaled "
+                        "e4m3, fp32 accumulation, bf16 output; WanTransformer3DFantasyModel.enable_fp8_qkv). Changes "
+                        "numerics (about 0.3e-2 rel-L2 per forward on top of bf16 on synthetic weights; real "
+                        "checkpoints unmeasured) and has no counterpart in the reference. With --fp8_attn the V "
+                        "projection writes the attention's V^T operand and the RMSNorm + RoPE kernel its Q operand. "
+                        "Measured: the chain from the LayerNorm to the attention's operands 1.25x, the 30-layer "
+                        "forward with --fp8_attn --fp8_ffn 1.027x over those two alone, 1.28x over bf16 (DESIGN.md, "
+                        "fp8 q/k/v).")
     p.add_argument("--window_parallel", action="store_true",
                    help="multi-GPU: spread the sliding windows of each step over the ranks instead of sequence "
                         "parallelism (long clips, SURVEY.md §8(e))")
@@ -264,6 +276,10 @@ def main(argv=None):
         print("fp8 attention: the DiT blocks' self-attention runs on MXFP8 operands (numerics differ from the bf16 "
               "path)")
         transformer3d.enable_fp8_attention()
+    if args.fp8_qkv:
+        print("fp8 q/k/v: the DiT blocks' self-attention q/k/v Linears run on MXFP8 operands (numerics differ from "
+              "the bf16 path)")
+        transformer3d.enable_fp8_qkv()
     if args.enable_teacache:
         coefficients = get_teacache_coefficients(root)
         if coefficients is not None:

@@ -3,7 +3,8 @@ python -m stableavatar_amd.kbench  -> one JSON line per kernel with TFLOP/s (ran
 Selectors: gemm, attn, gemmvar, attnvar, dit, ditvar, ...; gemmfp8 = the fp8 FFN mode's LayerNorm / ffn_up / ffn_down
 against the bf16 kernels, ditfp8 = the whole forward with the mode off and on; attnfp8 = the config-2 self-attention
 launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the whole forward with that mode off, on, and
-on together with the fp8 FFN."""
+on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (LayerNorm .. operands ready) in bf16, with the
+fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused."""
 from __future__ import annotations
 
 import json
@@ -280,6 +281,11 @@ def main(which=("gemm", "attn")):
         print(json.dumps(res[-1]), flush=True)
     if "attnfp8" in which:  # the fp8 attention mode's kernels against the bf16 launch, interleaved rounds
         res.extend(bench_fp8_attn())
+    if "qkvfp8" in which:  # the fp8 q/k/v mode's operand chains against the bf16 one, interleaved rounds
+        res.extend(bench_fp8_qkv())
+    if "ditfp8qkv" in which:  # whole-forward A/B of enable_fp8_qkv() on top of the other two modes, interleaved
+        res.append(bench_dit(fp8_qkv_ab=True))
+        print(json.dumps(res[-1]), flush=True)
     if "ditfp8attn" in which:  # whole-forward A/B of enable_fp8_attention() (and with enable_fp8_ffn()), interleaved
         res.append(bench_dit(fp8_attn_ab=True))
         print(json.dumps(res[-1]), flush=True)
@@ -342,6 +348,83 @@ def bench_fp8_attn(L=21504, H=12, B=3):
              bf16_tflops=round(fl / ms["bf16"] / 1e9, 1), fp8_kernel_tflops=round(fl / ms["fp8_kernel"] / 1e9, 1))
     print(json.dumps(r), flush=True)
     return [r]
+
+
+def bench_fp8_qkv(L=21504, H=12, B=3):
+    """The self-attention half of a config-2 block up to the point where the MXFP8 flash kernel's operands are ready
+    (M = 3 x 21 504 rows, dim 1536, 12 heads; fp8 attention on in all three), same process, interleaved rounds, median
+    of 3: the bf16 chain (LayerNorm, QKV GEMM, RMSNorm + RoPE, K means, pack), the fp8 q/k/v mode unfused (MXFP8
+    LayerNorm and GEMM, then the same three) and fused (q|k GEMM, V GEMM writing V^T, RMSNorm + RoPE writing Q, K means,
+    K pack).  One JSON line for the chains (ratio = bf16 ms / chain ms; whether the fused operands equal the unfused
+    ones byte for byte) and one with every stage timed alone in the same rounds."""
+    from .transformer import rope_table
+    dev, D = "cuda", 128
+    C, M = H * D, B * L
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(M, C, device=dev, generator=g)
+    mod = torch.randn(B, 2, C, device=dev, generator=g) * 0.3
+    w = (torch.randn(3 * C, C, device=dev, generator=g) / C ** 0.5).bfloat16()
+    bias = torch.randn(3 * C, device=dev, generator=g) * 0.1
+    nq, nk = 1 + 0.1 * torch.randn(C, device=dev, generator=g), 1 + 0.1 * torch.randn(C, device=dev, generator=g)
+    wq8 = ops.mxfp8_quant(w)
+    ln_bf, ln_mx = torch.empty(M, C, device=dev, dtype=torch.bfloat16), ops.Mx8.empty(M, C, dev)
+    qkv = torch.empty(M, 3 * C, device=dev, dtype=torch.bfloat16)
+    rows = [[b * L, L, b * L, L] for b in range(B)]
+    segs = torch.tensor(rows, dtype=torch.int32, device=dev)
+    vcol0, Rv = ops.attn_vcol0(rows)
+    vc = torch.tensor(vcol0, dtype=torch.int32, device=dev)
+    buf, buf_f = ops.AttnMx8(M, M, H, Rv, B, dev), ops.AttnMx8(M, M, H, Rv, B, dev)
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    kw = dict(shift=mod[:, 0], scale=mod[:, 1], rows_per_batch=L)
+    rope_kw = dict(rope=rope_table(D).to(dev), rows_per_batch=L, tok_offset=0, grid=(21, 32, 32), head_dim=D,
+                   n_frame_pairs=D // 2 - 2 * (D // 6), n_height_pairs=D // 6)
+    st = {
+        "ln_bf16": lambda: ops.layernorm_mod(x, ln_bf, 1e-6, **kw),
+        "ln_mxfp8": lambda: ops.layernorm_mod_mxfp8(x, ln_mx, 1e-6, **kw),
+        "qkv_bf16": lambda: ops.linear(ln_bf, w, bias, ops.EPI_BF16, out=qkv),
+        "qkv_mxfp8": lambda: ops.linear_mxfp8(ln_mx, wq8, bias, ops.EPI_BF16, out=qkv),
+        "qk_mxfp8": lambda: ops.linear_mxfp8(ln_mx, wq8[:2 * C], bias[:2 * C], ops.EPI_BF16, out=qkv[:, :2 * C]),
+        "v_mxfp8_vt": lambda: ops.linear_mxfp8_vt(ln_mx, wq8[2 * C:], bias[2 * C:], L, B, buf_f),
+        "rope": lambda: ops.qk_rmsnorm_rope(qkv, 0, C, nq, nk, C, 1e-6, **rope_kw),
+        "rope_mxfp8": lambda: ops.qk_rmsnorm_rope_mxfp8(qkv, 0, C, nq, nk, C, 1e-6, buf_f, **rope_kw),
+        "kmean": lambda: ops.attn_kmean(k, segs, B, H, buf.kmean, buf.kmean_work),
+        "pack": lambda: ops.attn_pack_mxfp8(q, k, v, segs, vc, B, L, L, H, buf, kmean=buf.kmean),
+        "kmean_f": lambda: ops.attn_kmean(k, segs, B, H, buf_f.kmean, buf_f.kmean_work),
+        "pack_k": lambda: ops.attn_pack_k_mxfp8(k, segs, B, L, H, buf_f, buf_f.kmean),
+    }
+    seq = {"bf16": ("ln_bf16", "qkv_bf16", "rope", "kmean", "pack"),
+           "unfused": ("ln_mxfp8", "qkv_mxfp8", "rope", "kmean", "pack"),
+           "fused": ("ln_mxfp8", "qk_mxfp8", "v_mxfp8_vt", "rope_mxfp8", "kmean_f", "pack_k")}
+
+    def chain(name):
+        def run():
+            for s_ in seq[name]:
+                st[s_]()
+        return run
+
+    fns = {n: chain(n) for n in seq}
+    fns.update(st)
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(3):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=10, warmup=1))
+        clocks.append(_sclk_mhz())
+    ms = {n: sorted(t)[1] for n, t in times.items()}
+    fns["unfused"]()
+    fns["fused"]()
+    torch.cuda.synchronize()
+    same = all(torch.equal(a, b) for a, b in ((buf.qq, buf_f.qq), (buf.qs, buf_f.qs), (buf.kq, buf_f.kq),
+                                              (buf.ks, buf_f.ks), (buf.vq, buf_f.vq), (buf.vs, buf_f.vs)))
+    r = {"kernel": "fp8qkv_chain", "M": M, "dim": C, "heads": H, "sclk_mhz": clocks, "fused_equals_unfused": same}
+    for n in seq:
+        r[f"{n}_ms"] = round(ms[n], 4)
+    r.update(ratio_unfused=round(ms["bf16"] / ms["unfused"], 3), ratio_fused=round(ms["bf16"] / ms["fused"], 3),
+             fused_vs_unfused=round(ms["unfused"] / ms["fused"], 3))
+    print(json.dumps(r), flush=True)
+    r2 = {"kernel": "fp8qkv_stages", "M": M}
+    r2.update({f"{n}_ms": round(ms[n], 4) for n in st})
+    print(json.dumps(r2), flush=True)
+    return [r, r2]
 
 
 def bench_fp8_ffn(M=3 * 21504, C=1536, FF=8960, rpb=21504):
@@ -488,13 +571,15 @@ def attn_clip_inputs(layers=(0, 15, 29)):
     return out
 
 
-def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False, fp8_attn_ab=False):
+def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False, fp8_attn_ab=False,
+              fp8_qkv_ab=False):
     """One full 30-layer DiT forward at config 2 (B=3 CFG, 21 latent frames at 64x64, L=21504).
     attn_variants: time the forward under each self-attention schedule, interleaved rounds.
     fp8_ab: the forward with enable_fp8_ffn() off and on (two models on the same weights), interleaved rounds,
     and the rel-L2 between their outputs.  fp8_attn_ab: the same for enable_fp8_attention() off, on, and on together
     with enable_fp8_ffn() (three models on the same weights), each output's rel-L2 against off, the graphics clock
-    after each round."""
+    after each round.  fp8_qkv_ab: four variants on the same weights -- off; attention + FFN; those + enable_fp8_qkv()
+    unfused; and fused -- each output's rel-L2 against off, whether fused equals unfused byte for byte."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -558,6 +643,35 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
             if k != "off":
                 r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
                 r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
+        return r
+    if fp8_qkv_ab:
+        modes = {"off": m}
+        for k in ("attn_ffn", "attn_ffn_qkv_unfused", "attn_ffn_qkv_fused"):
+            mm = WanTransformer3DFantasyModel(**cfg)
+            mm.load_state_dict(m.state_dict())
+            modes[k] = mm.to(dev)
+            modes[k].enable_fp8_attention()
+            modes[k].enable_fp8_ffn()
+            if k != "attn_ffn":
+                modes[k].enable_fp8_qkv()
+                modes[k]._fp8_qkv_fused = k.endswith("_fused")
+        times, clocks, outs = {k: [] for k in modes}, [], {}
+        with torch.no_grad():
+            for _ in range(3):
+                for k, mm in modes.items():
+                    f = lambda mm=mm: mm.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)  # noqa: E731
+                    times[k].append(_time(f, iters=2, warmup=1))
+                    outs[k] = f().float()
+                clocks.append(_sclk_mhz())
+        r = {"kernel": "dit_forward_fp8_qkv_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks,
+             "fused_equals_unfused": bool(torch.equal(outs["attn_ffn_qkv_fused"], outs["attn_ffn_qkv_unfused"]))}
+        for k in modes:
+            r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
+            if k != "off":
+                r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
+                r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
+        for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused"):
+            r[f"ratio_{k}_vs_attn_ffn"] = round(r["attn_ffn_ms"] / r[f"{k}_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os

@@ -1,7 +1,8 @@
 """MXFP8 self-attention as the fp8 attention mode computes it -- the definition the HIP kernels
 (csrc/attention_mxfp8.hip) are held to.  Plain torch, runs on the CPU.  `quantize` is mxfp8.quantize, head_dim is 128.
 
-Operands (sa_attn_pack_mxfp8 writes exactly these bytes):
+Operands (sa_attn_pack_mxfp8 writes exactly these bytes; with the fp8 q/k/v mode on as well, sa_qk_rmsnorm_rope_mxfp8
+writes Q, sa_attn_pack_k_mxfp8 K and sa_gemm_mxfp8_vt V^T, the same bytes):
   Q    quantize(fp32(q) * c) along D (four blocks per head), c = float32(scale) * 1.4426950408889634f: the log2(e)
        prescale is folded in before quantising, so the scores come out of the MFMA in exp2 units.
   K    quantize(fp32(k) - k_mean[seg][column]) along D.  k_mean is fp32 [nseg][heads * 128] (None: no subtraction).

@@ -353,6 +353,48 @@ def attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv_le
     return attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows)
 
 
+def linear_mxfp8_vt(x, weight, bias, rows_per_seg, nseg, buf):
+    """The V projection on MXFP8 operands written straight into buf's V^T operand (sa_gemm_mxfp8_vt): bit for bit
+    linear_mxfp8(EPI_BF16) followed by the V^T third of attn_pack_mxfp8 for nseg segments of rows_per_seg rows each
+    (attn_vcol0's layout for equal segments).  x: Mx8 [nseg * rows_per_seg, K], weight: Mx8 [heads * 128, K]."""
+    M, K = x.shape
+    N = weight.shape[0]
+    if weight.shape[1] != K or N != buf.heads * 128 or M != nseg * rows_per_seg:
+        raise ValueError(f"linear_mxfp8_vt: x {tuple(x.shape)}, weight {tuple(weight.shape)}, {nseg} x {rows_per_seg}")
+    if bias is not None:
+        _check(bias, torch.float32, "linear_mxfp8_vt.bias")
+    call("sa_gemm_mxfp8_vt", x.q.data_ptr(), x.q.stride(0), x.s.data_ptr(), x.s.stride(0), weight.q.data_ptr(),
+         weight.q.stride(0), weight.s.data_ptr(), weight.s.stride(0), _p(bias), buf.vq.data_ptr(), buf.vs.data_ptr(),
+         buf.Rv, M, N, K, rows_per_seg, nseg, _stream())
+    return buf
+
+
+def attn_pack_k_mxfp8(k, segs, nseg, max_kv_len, heads, buf, kmean=None):
+    """the K third of attn_pack_mxfp8 alone (sa_attn_pack_k_mxfp8)"""
+    _check(k, torch.bfloat16, "attn_pack_k_mxfp8.k")
+    assert k.stride(-1) == 1 and segs.dtype == torch.int32 and segs.is_cuda
+    assert buf.heads == heads and buf.kq.shape[0] >= k.shape[0]
+    call("sa_attn_pack_k_mxfp8", k.data_ptr(), k.stride(0), segs.data_ptr(), nseg, max_kv_len, heads, _p(kmean),
+         buf.kq.data_ptr(), buf.ks.data_ptr(), _stream())
+    return buf
+
+
+def qk_rmsnorm_rope_mxfp8(x, q_col, k_col, wq, wk, C, eps, buf, scale=None, rope=None, rows_per_batch=0, tok_offset=0,
+                          grid=(1, 1, 1), head_dim=128, n_frame_pairs=0, n_height_pairs=0, M=None):
+    """qk_rmsnorm_rope whose q leaves as buf's MXFP8 Q operand instead of going back in place
+    (sa_qk_rmsnorm_rope_mxfp8): bit for bit qk_rmsnorm_rope followed by the Q third of attn_pack_mxfp8; k in place."""
+    _check(x, torch.bfloat16, "qk_rmsnorm_rope_mxfp8.x")
+    M = x.shape[0] if M is None else M
+    assert buf.heads * 128 == C and buf.qq.shape[0] >= M
+    if scale is None:
+        scale = 128 ** -0.5
+    F, H, W = grid
+    call("sa_qk_rmsnorm_rope_mxfp8", x.data_ptr(), x.stride(0), q_col, k_col, wq.data_ptr(), _p(wk), M, C, head_dim,
+         float(eps), _p(rope), rows_per_batch, tok_offset, F, H, W, n_frame_pairs, n_height_pairs, buf.qq.data_ptr(),
+         buf.qq.stride(0), buf.qs.data_ptr(), buf.qs.stride(0), float(scale), _stream())
+    return x
+
+
 def qk_rmsnorm_rope(x, q_col, k_col, wq, wk, C, eps, rope=None, rows_per_batch=0, tok_offset=0, grid=(1, 1, 1),
                     head_dim=128, n_frame_pairs=0, n_height_pairs=0, M=None):
     M = x.shape[0] if M is None else M

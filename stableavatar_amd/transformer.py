@@ -242,6 +242,10 @@ class WanTransformer3DFantasyModel(nn.Module):
         self.attn_kernel = 0  # self-attention schedule (sa_attn_fwd_ex; 0 = auto), for in-situ A/B
         self._fp8_ffn = False  # enable_fp8_ffn(): the blocks' FFN GEMMs on MXFP8 operands
         self._fp8_attn = False  # enable_fp8_attention(): the blocks' self-attention on MXFP8 operands
+        self._fp8_qkv = False  # enable_fp8_qkv(): the blocks' self-attention q/k/v Linears on MXFP8 operands
+        # with _fp8_qkv and _fp8_attn both on, the single-GPU sites write the attention operands where their values are
+        # made (_self_attention_rows); False: the mode's GEMM, then _self_attn -- the same output bytes (for the A/B)
+        self._fp8_qkv_fused = True
         self._packed = None
         self._ws = {}
         self._ctx_cache = None
@@ -361,6 +365,25 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._fp8_attn = enabled
             self._ws = {}
 
+    def enable_fp8_qkv(self, enabled=True):
+        """MI355X addition (no counterpart in the reference; changes numerics): the q, k and v Linears of every DiT
+        block's self-attention (1B:383-413) run on MXFP8 operands -- the bf16 norm1 + modulate output and the bf16
+        weights quantised by mxfp8.quantize, fp32 accumulation, bias, bf16 rounding; RMSNorm, RoPE and the attention
+        see that bf16 result as before.  The vocal projector and cross-attention are untouched; independent of
+        enable_fp8_ffn() and enable_fp8_attention(), every combination works.  With the mode on the single-GPU sites
+        keep V in rows: sa_gemm_mxfp8 has no SA_EPI_BF16_TP32, so the bf16 V^T attention kernel 3 is not used.  Together
+        with enable_fp8_attention() those sites write the attention's operands where the values are made (V^T from
+        the V GEMM's epilogue, Q from the RMSNorm + RoPE kernel), bit-identical to the separate pack.  The
+        sequence-parallel sites use the mode for the GEMM only (the exchange carries bf16).  Toggling drops the packed
+        weights and the workspace, as enable_fp8_ffn does."""
+        enabled = bool(enabled)
+        if enabled and self.dim % 128:
+            raise ValueError(f"enable_fp8_qkv: dim {self.dim} must be a multiple of 128")
+        if enabled != self._fp8_qkv:
+            self._fp8_qkv = enabled
+            self._packed = None
+            self._ws = {}
+
     def _self_attn(self, ws, q, k, v, out, segs, nseg, max_q_len, heads, kernel=0, o_rows=None, split_tiles=0):
         """One self-attention launch of a DiT block: ops.attention, or with enable_fp8_attention() the K means, the
         operand pack and the MXFP8 flash kernel (ops.attention_mxfp8; no key split there).  The operand buffers live
@@ -438,7 +461,10 @@ class WanTransformer3DFantasyModel(nn.Module):
             L = SimpleNamespace()
             L.w_qkv = cat_bf(p + "self_attn.q.weight", p + "self_attn.k.weight", p + "self_attn.v.weight")
             L.b_qkv = cat_f(p + "self_attn.q.bias", p + "self_attn.k.bias", p + "self_attn.v.bias")
-            # views for the single-GPU V^T path: q|k rows into the QKV rows, v into V^T (EPI_BF16_TP32)
+            if self._fp8_qkv:  # quantised along K on the GPU (= mxfp8.quantize), the bf16 copy dropped
+                L.w_qkv = ops.mxfp8_quant(L.w_qkv)
+            # views for the single-GPU V^T path: q|k rows into the QKV rows, v into V^T (EPI_BF16_TP32, or with
+            # enable_fp8_qkv() + enable_fp8_attention() sa_gemm_mxfp8_vt)
             L.w_qk, L.b_qk = L.w_qkv[:2 * self.dim], L.b_qkv[:2 * self.dim]
             L.w_v, L.b_v = L.w_qkv[2 * self.dim:], L.b_qkv[2 * self.dim:]
             L.nq, L.nk = f32(p + "self_attn.norm_q.weight"), f32(p + "self_attn.norm_k.weight")
@@ -510,8 +536,9 @@ class WanTransformer3DFantasyModel(nn.Module):
                 vt=None,  # V^T [dim, M rounded up to 64] of the single-GPU self-attention, allocated on first use
                 attn8={},  # enable_fp8_attention(): ops.AttnMx8 operand buffers per segment table (_self_attn)
             )
-            if self._fp8_ffn:  # the FFN's operands as MXFP8: its LayerNorm output and its hidden activations
+            if self._fp8_ffn or self._fp8_qkv:  # a LayerNorm output as MXFP8 (the FFN's or the q/k/v Linears' input)
                 ws.modq = ops.Mx8.empty(M, dim, dev)
+            if self._fp8_ffn:  # the FFN's hidden activations as MXFP8
                 ws.ffn = ops.Mx8.empty(M, self.ffn_dim, dev)
             self._ws = {key: ws}  # keep one shape at a time
         return ws
@@ -689,9 +716,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         for b, st in enumerate(rstreams if sa else []):  # self-attention inputs (1B:675-676) and the Q/K/V exchange
             rs = slice(b * Lc, (b + 1) * Lc)
             with torch.cuda.stream(st):
-                ops.layernorm_mod(x[rs], ws.mod[rs], eps, shift=em[b:b + 1, 0], scale=em[b:b + 1, 1],
-                                  rows_per_batch=Lc)
-                ops.linear(ws.mod[rs], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=ws.qkv[rs])
+                self._qkv(L, x[rs], ws, rs, em[b:b + 1, 0], em[b:b + 1, 1], Lc)
                 ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, eps, b_offset=b, **pack_kw, **rope_kw)
                 pend.append(ex.heads([b]))
         for b, st in enumerate(rstreams if sa else []):  # attention over every key, head outputs back to the owners
@@ -729,6 +754,25 @@ class WanTransformer3DFantasyModel(nn.Module):
                 ops.linear(att, L.w_co, L.b_co, ops.EPI_RES_F32, out=xr, residual=xr)
                 self._ffn(L, xr, ws, rs, em[b:b + 1, 3], em[b:b + 1, 4], em[b:b + 1, 5], Lc)
 
+    def _norm1(self, x, ws, rows, shift, scale, Lc):
+        """norm1 + modulate (1B:675) of the rows x of the residual stream into workspace rows `rows`: bf16 ws.mod, or
+        with enable_fp8_qkv() MXFP8 ws.modq (bf16 output followed by the quantiser, in one kernel)"""
+        if self._fp8_qkv:
+            return ops.layernorm_mod_mxfp8(x, ws.modq[rows], self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
+        return ops.layernorm_mod(x, ws.mod[rows], self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
+
+    def _qkv(self, L, x, ws, rows, shift, scale, Lc, normed=False, out=None):
+        """The q|k|v Linears of a block's self-attention (1B:383-390) for the rows x of the residual stream (workspace
+        rows `rows`): norm1 + modulate (unless `normed`: _norm1 already ran), then the fused QKV GEMM into `out`
+        (default ws.qkv[rows]) as bf16.  With enable_fp8_qkv() the LayerNorm writes MXFP8 and the GEMM runs on the
+        block-scaled fp8 MFMA; off, exactly the bf16 calls."""
+        if not normed:
+            self._norm1(x, ws, rows, shift, scale, Lc)
+        out = ws.qkv[rows] if out is None else out
+        if self._fp8_qkv:
+            return ops.linear_mxfp8(ws.modq[rows], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=out)
+        return ops.linear(ws.mod[rows], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=out)
+
     def _ffn(self, L, x, ws, rows, shift, scale, gate, Lc):
         """The FFN third of a block (1B:687-691) on the rows x of the residual stream (workspace rows `rows`): norm2 +
         modulate, ffn.0 + GELU, ffn.2 + gated residual into x.  With enable_fp8_ffn() the LayerNorm writes MXFP8,
@@ -752,8 +796,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         enter the block identical (forward_window shared_rows), and every rank takes this path together"""
         dim, eps = self.dim, self.eps
         rs = slice(0, Lc)
-        ops.layernorm_mod(x[rs], ws.mod[rs], eps, shift=em[0:1, 0], scale=em[0:1, 1], rows_per_batch=Lc)
-        ops.linear(ws.mod[rs], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=ws.qkv[rs])
+        self._qkv(L, x[rs], ws, rs, em[0:1, 0], em[0:1, 1], Lc)
         ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, eps, b_offset=0, **pack_kw, **rope_kw)
         ex.heads([0]).wait()
         ev0 = self._record_event()
@@ -770,14 +813,31 @@ class WanTransformer3DFantasyModel(nn.Module):
     def _self_attention_rows(self, pk, L, x, ws, em, nb, Lc, Lp, use_vt, rope_kw, dev, batch, normed=False):
         """The self-attention half of a block (1B:675-679) on the first nb CFG rows of the single-GPU layout: LN +
         modulate (unless `normed`), q|k (+ v as V^T for kernel 3, or q|k|v rows), RMSNorm + RoPE, attention,
-        O-projection + gated residual into x"""
+        O-projection + gated residual into x.  With enable_fp8_qkv() and enable_fp8_attention() (and _fp8_qkv_fused)
+        the fused chain: q|k GEMM, the V GEMM writing the V^T operand, RMSNorm + RoPE writing the Q operand, K means,
+        K pack, the MXFP8 flash kernel."""
         dim, H_ = self.dim, self.num_heads
         r = slice(0, nb * Lc)
         xr, mod, qkv, att = x[r], ws.mod[r], ws.qkv[r], ws.att[r]
         if not normed:
-            ops.layernorm_mod(xr, mod, self.eps, shift=em[:nb, 0], scale=em[:nb, 1], rows_per_batch=Lc)
+            self._norm1(xr, ws, r, em[:nb, 0], em[:nb, 1], Lc)
         segs = self._segs.get(("self", nb, Lp), [[b * Lp, Lp, b * Lp, Lp] for b in range(nb)], dev)
-        if use_vt:
+        if self._fp8_qkv and self._fp8_attn and self._fp8_qkv_fused:
+            assert Lc == Lp and not use_vt
+            vcol0, Rv, max_kv = self._segs.vt_layout(segs)
+            key = (id(segs), nb * Lc, nb * Lc, H_)
+            buf = ws.attn8.get(key)
+            if buf is None:
+                buf = ws.attn8[key] = ops.AttnMx8(nb * Lc, nb * Lc, H_, Rv, nb, dev)
+            modq = ws.modq[r]
+            ops.linear_mxfp8(modq, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
+            ops.linear_mxfp8_vt(modq, L.w_v, L.b_v, Lp, nb, buf)
+            ops.qk_rmsnorm_rope_mxfp8(qkv, 0, dim, L.nq, L.nk, dim, self.eps, buf, **rope_kw)
+            ev0 = self._record_event()
+            km = ops.attn_kmean(qkv[:, dim:2 * dim], segs, nb, H_, buf.kmean, buf.kmean_work)
+            ops.attn_pack_k_mxfp8(qkv[:, dim:2 * dim], segs, nb, max_kv, H_, buf, km)
+            ops.attn_fwd_mxfp8(buf, att, segs, vcol0, nb, Lp, H_)
+        elif use_vt:
             # q|k into the QKV rows, v straight into V^T (keys in P's order per 32) for attention kernel 3
             ops.linear(mod, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
             ops.linear(mod, L.w_v, L.b_v, ops.EPI_BF16_TP32, out=ws.vt)
@@ -785,7 +845,7 @@ class WanTransformer3DFantasyModel(nn.Module):
             ev0 = self._record_event()
             ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_, kernel=ops.ATTN_VT_P32)
         else:
-            ops.linear(mod, L.w_qkv, L.b_qkv, ops.EPI_BF16, out=qkv)
+            self._qkv(L, xr, ws, r, None, None, Lc, normed=True)
             ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **rope_kw)
             ev0 = self._record_event()
             self._self_attn(ws, qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs, nb, Lp, H_,
@@ -983,7 +1043,7 @@ class WanTransformer3DFantasyModel(nn.Module):
             use_cross3 = (ctx.img_len > 0 and G % 256 == 0 and (rank * Lc) % 256 == 0 and (rank + 1) * Lc <= S
                           and os.environ.get("SA_CROSS3", "1") != "0")
             x = ws.x
-            use_vt = not SP and not self._fp8_attn and self._vt_attention(Lp, dev)
+            use_vt = not SP and not self._fp8_attn and not self._fp8_qkv and self._vt_attention(Lp, dev)
             # shared_rows: the first block's self-attention half once (single-GPU layout, or the one-stream and
             # per-row-stream Ulysses schedules)
             dedup = shared_rows and broadcast and B > 1 and (not SP or sp_streams or not (sp_rows or sp_rows_x))
@@ -1035,7 +1095,7 @@ class WanTransformer3DFantasyModel(nn.Module):
                                         sa=not first_shared)
                     continue
                 if not first_shared:  # self-attention (1B:675-679)
-                    ops.layernorm_mod(x, ws.mod, self.eps, shift=em[:, 0], scale=em[:, 1], rows_per_batch=Lc)
+                    self._norm1(x, ws, slice(None), em[:, 0], em[:, 1], Lc)
                     if SP and sp_rows:
                         # Ulysses pipelined over the CFG rows: row b's Q/K/V exchange is issued right after its
                         # QKV GEMM + pack (so it travels under rows b+1..'s GEMMs), row b's attention waits
@@ -1044,7 +1104,7 @@ class WanTransformer3DFantasyModel(nn.Module):
                         pend = []
                         for b in range(B):
                             rs = slice(b * Lc, (b + 1) * Lc)
-                            ops.linear(ws.mod[rs], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=ws.qkv[rs])
+                            self._qkv(L, x[rs], ws, rs, None, None, Lc, normed=True)
                             ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, self.eps, b_offset=b, **pack_kw, **rope_kw)
                             pend.append(ex.heads([b]))
                         back = []
@@ -1068,13 +1128,13 @@ class WanTransformer3DFantasyModel(nn.Module):
                             pend = []
                             for b in range(B):
                                 rs = slice(b * Lc, (b + 1) * Lc)
-                                ops.linear(ws.mod[rs], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=ws.qkv[rs])
+                                self._qkv(L, x[rs], ws, rs, None, None, Lc, normed=True)
                                 ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, self.eps, b_offset=b, **pack_kw, **rope_kw)
                                 pend.append(ex.heads([b]))
                             for p_ in pend:
                                 p_.wait()
                         else:  # one exchange per direction for all rows
-                            ops.linear(ws.mod, L.w_qkv, L.b_qkv, ops.EPI_BF16, out=ws.qkv)
+                            self._qkv(L, x, ws, slice(None), None, None, Lc, normed=True)
                             ops.qkv_pack(ws.qkv, L.nq, L.nk, dim, self.eps, **pack_kw, **rope_kw)
                             ex.heads(range(B)).wait()
                         # Ulysses: full-sequence attention of this rank's (query part, head group), outputs written
