@@ -700,7 +700,7 @@ extern "C" int sa_conv3d_cl_down(const void* x, int T_out, int H_in, int W_in, i
 
 extern "C" int sa_vae_rmsnorm_silu(const void* x, void* y, const float* gamma, int64_t rows, int C, int do_silu,
                                    void* stream) {
-  if (!x || !y || !gamma || C % 8 || C > 512) return SA_ERR_ARG;
+  if (!x || !y || !gamma || rows <= 0 || C <= 0 || C % 8 || C > 512) return SA_ERR_ARG;
   const int g8 = C / 8;
   hipStream_t st = (hipStream_t)stream;
   const char* e = getenv("SA_RMS3");
@@ -740,7 +740,7 @@ extern "C" int sa_vae_rmsnorm_silu(const void* x, void* y, const float* gamma, i
 
 extern "C" int sa_vae_input(const float* z, int Cz, int64_t THW, const float* mean, const float* stdv, void* out,
                             int Cp, void* stream) {
-  if (!z || !out || Cp < Cz) return SA_ERR_ARG;
+  if (!z || !mean || !stdv || !out || Cz <= 0 || THW <= 0 || Cp < Cz) return SA_ERR_ARG;
   hipLaunchKernelGGL(vae_input_kernel, dim3(nblk(THW * Cp, 256)), dim3(256), 0, (hipStream_t)stream, z, Cz, THW,
                      mean, stdv, (bf16*)out, Cp);
   SA_LAUNCH_CHECK();
@@ -748,7 +748,7 @@ extern "C" int sa_vae_input(const float* z, int Cz, int64_t THW, const float* me
 }
 
 extern "C" int sa_vae_output(const float* in, int C_stride, int C, int64_t THW, float* out, int post, void* stream) {
-  if (!in || !out || C > C_stride) return SA_ERR_ARG;
+  if (!in || !out || C <= 0 || THW <= 0 || C > C_stride) return SA_ERR_ARG;
   hipLaunchKernelGGL(vae_output_kernel, dim3(nblk(THW * C, 256)), dim3(256), 0, (hipStream_t)stream, in, C_stride, C,
                      THW, out, post);
   SA_LAUNCH_CHECK();
@@ -757,7 +757,7 @@ extern "C" int sa_vae_output(const float* in, int C_stride, int C, int64_t THW, 
 
 extern "C" int sa_vae_latent_out(const float* in, int C_stride, int Cz, int64_t THW, const float* mean,
                                  const float* stdv, float* out, void* stream) {
-  if (!in || !out || !mean || !stdv || 2 * Cz > C_stride) return SA_ERR_ARG;
+  if (!in || !out || !mean || !stdv || Cz <= 0 || THW <= 0 || 2 * Cz > C_stride) return SA_ERR_ARG;
   hipLaunchKernelGGL(vae_latent_out_kernel, dim3(nblk(THW * 2 * Cz, 256)), dim3(256), 0, (hipStream_t)stream, in,
                      C_stride, Cz, THW, mean, stdv, out);
   SA_LAUNCH_CHECK();
@@ -775,7 +775,7 @@ extern "C" int sa_softmax_rows(const float* s, int64_t ld_s, void* p, int64_t ld
 
 extern "C" int sa_transpose_bf16(const void* in, int64_t ld_in, int64_t stride_in, void* out, int64_t ld_out,
                                  int64_t stride_out, int rows, int cols, int batch, void* stream) {
-  if (!in || !out) return SA_ERR_ARG;
+  if (!in || !out || rows <= 0 || cols <= 0 || batch <= 0) return SA_ERR_ARG;
   dim3 grid(nblk(cols, 32), nblk(rows, 32), batch);
   hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)in, ld_in, stride_in,
                      (bf16*)out, ld_out, stride_out, rows, cols);
