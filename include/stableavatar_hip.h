@@ -205,6 +205,22 @@ int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void* k, const 
                       const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim, const int32_t* o_rows,
                       void* stream);
 
+/* sa_attn_fwd_mxfp8 with the keys of the LAST split_tiles tiles split in two halves, as sa_attn_fwd_split does for
+ * the bf16 kernel.  Tile = (segment, head, 256-query block), numbered (seg * heads + h) * nqb + qb with
+ * nqb = ceil(max_q_len / 256); tiles that hold no query count.  The halves of a tile meet at key
+ * kper = ceil128(ceil(kv_len / 2)); each is a workgroup of its own running the flash loop over its keys and writing
+ * fp32 partials to work -- its unnormalised O, the running maximum it used and its row sum -- and a second launch
+ * merges them: o = (w0 O0 + w1 O1) / (w0 l0 + w1 l1), w_h = exp2(m_h - max(m0, m1)), w_h = 0 for a half whose maximum
+ * stands so far below the other's that each of its P rounds to zero against the row's maximum (the flash loop's own
+ * drop rule; mxfp8_attn.attend_split is the definition).  The rows of whole tiles, and of split tiles whose second
+ * half is empty (kv_len <= 128), are the bytes sa_attn_fwd_mxfp8 writes; a split tile of a segment with kv_len == 0
+ * writes zeros.  work: >= split_tiles * 2 * 256 * (128 + 2) floats, 16-B aligned (layout: csrc/attention_mxfp8.hip);
+ * 0 < split_tiles <= the tile count.  Every argument is checked before the first HIP call. */
+int sa_attn_fwd_mxfp8_split(const void* q, const void* q_scales, const void* k, const void* k_scales, const void* vt,
+                            const void* vt_scales, int64_t Rv, void* o, int64_t o_stride, const int32_t* segs,
+                            const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim,
+                            const int32_t* o_rows, int split_tiles, void* work, int64_t work_bytes, void* stream);
+
 /* ---- fp8 q/k/v mode feeding the fp8 attention directly (opt-in; no counterpart in the reference) ----
  * Three entry points that write the operands of sa_attn_fwd_mxfp8 where their values are made.  Each is bit-identical
  * to the pair of calls it replaces, and checks every argument before its first HIP call. */

@@ -2,7 +2,9 @@
 point-to-point exchanges and the head all-gather stubbed out (no data moves; the exchange buffers hold random
 values so the kernels see ordinary data).  Measures what sequence parallelism costs in kernel efficiency alone
 (GEMM tiles and attention workgroups per rank at 1/N of the tokens), i.e. the upper bound of the N-GPU
-speedup before any xGMI time.  usage: python scripts/sp_rank_compute.py [N ...]"""
+speedup before any xGMI time.  usage: python scripts/sp_rank_compute.py [N ...]
+SA_SPRC_FP8=attn,ffn,qkv enables the fp8 modes named; SA_SPRC_SPLIT=1,0 times every case once per SA_ATTN_SPLIT value
+listed (the attention's key-split tail on / off), the values interleaved forward by forward."""
 import json
 import os
 import sys
@@ -22,6 +24,9 @@ cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096
 m = WanTransformer3DFantasyModel(**cfg)
 m.load_state_dict(synthetic.fill_state_dict(param_shapes(cfg), 0, backend="torch", device=dev))
 m = m.to(dev)
+fp8 = [f for f in os.environ.get("SA_SPRC_FP8", "").split(",") if f]
+for f in fp8:
+    {"attn": m.enable_fp8_attention, "ffn": m.enable_fp8_ffn, "qkv": m.enable_fp8_qkv}[f]()
 g = torch.Generator(device=dev).manual_seed(0)
 lat = torch.randn(1, 16, 21, 64, 64, device=dev, generator=g).bfloat16()
 y = torch.randn(1, 20, 21, 64, 64, device=dev, generator=g).bfloat16().expand(3, -1, -1, -1, -1).contiguous()
@@ -50,6 +55,7 @@ def fwd():
 
 res = []
 modes = os.environ.get("SA_SPRC_MODES", "1").split(",")  # SA_SP_OVERLAP values to time at each degree > 1
+splits = os.environ["SA_SPRC_SPLIT"].split(",") if os.environ.get("SA_SPRC_SPLIT") else [None]
 with torch.no_grad():
     for N, ov in [(n, o) for n in degrees for o in (modes if n > 1 else ["1"])]:
         os.environ["SA_SP_OVERLAP"] = ov
@@ -62,20 +68,32 @@ with torch.no_grad():
             ex = m._sp_ex[1]
             for buf in (ex.q, ex.kv, ex.obuf):
                 buf.normal_()
-        for _ in range(2):
-            fwd()
+        for sv in splits:
+            if sv is not None:
+                os.environ["SA_ATTN_SPLIT"] = sv
+            for _ in range(2):
+                fwd()
         torch.cuda.synchronize()
-        ts, hs = [], []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            fwd()
-            hs.append((time.perf_counter() - t0) * 1e3)  # host enqueue time of the forward (no sync inside)
-            torch.cuda.synchronize()
-            ts.append((time.perf_counter() - t0) * 1e3)
-        r = {"kernel": "sp_rank_forward", "degree": N, "sp_overlap": ov, "ms": round(sorted(ts)[1], 2),
-             "host_enqueue_ms": round(sorted(hs)[1], 2)}
-        res.append(r)
-        print(json.dumps(r), flush=True)
+        ts, hs = {sv: [] for sv in splits}, {sv: [] for sv in splits}
+        for _ in range(3 if splits == [None] else 5):
+            for sv in splits:
+                if sv is not None:
+                    os.environ["SA_ATTN_SPLIT"] = sv
+                t0 = time.perf_counter()
+                fwd()
+                hs[sv].append((time.perf_counter() - t0) * 1e3)  # host enqueue time of the forward (no sync inside)
+                torch.cuda.synchronize()
+                ts[sv].append((time.perf_counter() - t0) * 1e3)
+        for sv in splits:
+            n = len(ts[sv])
+            r = {"kernel": "sp_rank_forward", "degree": N, "sp_overlap": ov, "ms": round(sorted(ts[sv])[n // 2], 2),
+                 "host_enqueue_ms": round(sorted(hs[sv])[n // 2], 2)}
+            if fp8:
+                r["fp8"] = fp8
+            if sv is not None:
+                r.update(attn_split=sv, rounds_ms=[round(x, 2) for x in ts[sv]])
+            res.append(r)
+            print(json.dumps(r), flush=True)
 base = res[0]["ms"] if res[0]["degree"] == 1 else None
 if base:
     for r in res:

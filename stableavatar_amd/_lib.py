@@ -30,6 +30,7 @@ SIGNATURES = {
     "sa_attn_kmean": "plpiiippp",
     "sa_attn_pack_mxfp8": "plplplppiiiiifppppppplp",
     "sa_attn_fwd_mxfp8": "pppppplplppiiiipp",
+    "sa_attn_fwd_mxfp8_split": "pppppplplppiiiipiplp",
     "sa_gemm_mxfp8_vt": "plplplplpppliiiiip",
     "sa_qk_rmsnorm_rope_mxfp8": "pliippiiifpiiiiiiiplplfp",
     "sa_attn_pack_k_mxfp8": "plpiiipppp",

@@ -16,6 +16,21 @@
 // K^ and V^T tiles (128 rows x 128 B each, gemm.hip's swz128 image) and their scale dwords are staged by
 // global_load ... lds into a 2-stage ring, one barrier per block; rows past kv_len are clamped to the last key (read
 // again, masked to P = 0), so every load stays inside the operand.
+//
+// sa_attn_fwd_mxfp8_split: the same body with SPLIT set (attention.hip's key-split launch on this kernel).  Tiles are
+// numbered (seg * heads + h) * nqb + qb; a 1-D grid whose first split_full workgroups run whole tiles exactly as
+// above and whose last 2 x split_tiles are the two key halves of the last split_tiles tiles.  The halves meet at
+// kper = ceil128(ceil(kv_len / 2)), so the second half's V^T columns start on a block boundary.  A half runs the same
+// block loop over its keys and writes fp32 partials to its block of `work` instead of the output; block
+// (split tile s, half) starts at float (2 s + half) * 256 * 130 and holds
+//   O  [8][256][16]  unnormalised O of d tile dt, query row r of the tile, d = 16 dt + j (a wave's store of one d
+//                    tile is 1 KB contiguous),
+//   m  [256]         the running maximum the half used, P_SHIFT - cinit (it lags the half's true maximum by at most
+//                    LAG; O and l are relative to it), -inf for a half with no keys,
+//   l  [256]         the row sum of the rounded P (times 2^P_SHIFT, as O).
+// attn_mx_split_merge_kernel: o = (w0 O0 + w1 O1) / (w0 l0 + w1 l1), w_h = exp2(m_h - max(m0, m1)), and w_h = 0
+// for a half whose reported maximum stands more than FLUSH_GAP below the other's: its true maximum then stands
+// more than 10 + P_SHIFT below the row's, the definition's drop rule (mxfp8_attn.attend_split).  No keys at all: zeros.
 #include "mxfp8.h"
 
 namespace {
@@ -46,6 +61,12 @@ struct FwdArgs {
   const int* segs; const int* vcol0; const int* orows;
   int heads;
 };
+// the key-split launch (the header comment): tile decode and the partials
+struct SplitArgs {
+  int nqb, split_full;  // query blocks per (segment, head); the number of whole tiles
+  float* work;
+};
+constexpr int WBLK = QBW * (D + 2);  // floats per (split tile, half)
 
 template <int OFF>
 __device__ __forceinline__ void ds_b128(u32x4& d, uint32_t addr) {
@@ -81,18 +102,59 @@ __device__ __forceinline__ void read4(u32x4 (&lo)[4], u32x4 (&hi)[4], uint32_t (
                  "+v"(sc[0]), "+v"(sc[1]), "+v"(sc[2]), "+v"(sc[3])::"memory");
 }
 
-__global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a) {
+// (a template on the kernel itself: called as an inlined body from two wrappers, as attention.hip's split is, the
+// compiler schedules the unsplit instantiation differently; this way its instruction stream is what it was)
+template <bool SPLIT>
+__global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a, SplitArgs sp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nx = gridDim.x, ny = gridDim.y;
-  const int flat = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z);
-  const int qb = flat % nx, h = (flat / nx) % ny, seg = flat / (nx * ny);
+  int qb, h, seg, half = -1, stile = 0;
+  if constexpr (SPLIT) {
+    int tile;
+    if ((int)blockIdx.x < sp.split_full) {
+      tile = xcd_remap(blockIdx.x, sp.split_full);
+    } else {
+      const int idx = blockIdx.x - sp.split_full;
+      stile = idx >> 1;
+      half = idx & 1;
+      tile = sp.split_full + stile;
+    }
+    qb = tile % sp.nqb;
+    h = (tile / sp.nqb) % a.heads;
+    seg = tile / (sp.nqb * a.heads);
+  } else {
+    const int nx = gridDim.x, ny = gridDim.y;
+    const int flat = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z);
+    qb = flat % nx, h = (flat / nx) % ny, seg = flat / (nx * ny);
+  }
   const int* sg = a.segs + seg * 4;
-  const int q_row0 = sg[0], q_len = sg[1], kv_row0 = sg[2], kv_len = sg[3];
+  const int q_row0 = sg[0], q_len = sg[1];
+  int kv_row0 = sg[2], kv_len = sg[3];
   if (qb * QBW >= q_len) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int C = a.heads * D, CS = a.heads * 4;  // row bytes of Q^ / K^, of their scales
+  long vc0 = a.vcol0[seg];
+  float* const wblk = SPLIT && half >= 0 ? sp.work + ((long)stile * 2 + half) * WBLK : nullptr;
+  if (SPLIT && half >= 0) {
+    // a segment whose V^T columns leave the operand is skipped whole (the merge skips it too)
+    if (kv_len > 0 && (vc0 < 0 || vc0 + ((long)kv_len + KVB - 1) / KVB * KVB > a.Rv)) return;
+    const int kper = ((kv_len + 1) / 2 + KVB - 1) / KVB * KVB;  // this half's keys: whole blocks in the first half
+    if (half == 0) {
+      kv_len = min(kv_len, kper);
+    } else {
+      kv_row0 += kper;
+      kv_len -= kper;
+      vc0 += kper;
+    }
+    if (kv_len <= 0) {  // a half with no keys: m = -inf, l = 0, O = 0
+      for (int i = tid; i < QBW * D; i += 512) wblk[i] = 0.f;
+      if (tid < QBW) {
+        wblk[QBW * D + tid] = -__builtin_inff();
+        wblk[QBW * D + QBW + tid] = 0.f;
+      }
+      return;
+    }
+  }
   const int nkb = (kv_len + KVB - 1) / KVB;
-  const long vc0 = a.vcol0[seg];
   if (kv_len <= 0) {
     for (int i = tid; i < QBW * (D / 8); i += 512) {
       const int qi = qb * QBW + i / (D / 8);
@@ -271,6 +333,19 @@ __global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a) {
     }
   }
 
+  if (SPLIT && half >= 0) {  // partials: this lane's d = 16 dt + 4 g + e of query row `row`, the row's max and sum
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      const int row = wave * 32 + qt * 16 + r16;
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) *(f32x4*)(wblk + (dt * QBW + row) * 16 + 4 * g) = O[dt][qt];
+      if (g == 0) {
+        wblk[QBW * D + row] = P_SHIFT - cinit[qt];
+        wblk[QBW * D + QBW + row] = L[qt][0];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int qi = qb * QBW + wave * 32 + qt * 16 + r16;
@@ -284,6 +359,39 @@ __global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a) {
       const f32x4& v = O[dt][qt];
       *(bf16x4*)(op + dt * 16) = (bf16x4){f2bf(v[0] * inv), f2bf(v[1] * inv), f2bf(v[2] * inv), f2bf(v[3] * inv)};
     }
+  }
+}
+
+// the two key halves of each split tile -> the output (the header comment).  A thread takes four d of a row: 32
+// threads a row, so a wave reads 128 contiguous bytes of each half's d tile and writes two 256-byte rows
+__global__ __launch_bounds__(256) void attn_mx_split_merge_kernel(FwdArgs a, SplitArgs sp) {
+  const int stile = blockIdx.x, tile = sp.split_full + stile;
+  const int qb = tile % sp.nqb, h = (tile / sp.nqb) % a.heads, seg = tile / (sp.nqb * a.heads);
+  const int* sg = a.segs + seg * 4;
+  const int q_row0 = sg[0], q_len = sg[1], kv_len = sg[3];
+  if (qb * QBW >= q_len) return;
+  const long vc0 = a.vcol0[seg];
+  if (kv_len > 0 && (vc0 < 0 || vc0 + ((long)kv_len + KVB - 1) / KVB * KVB > a.Rv)) return;  // skipped, as the halves
+  const float* w0 = sp.work + (long)stile * 2 * WBLK;
+  const float* w1 = w0 + WBLK;
+  for (int i = threadIdx.x; i < QBW * (D / 4); i += 256) {
+    const int row = i / (D / 4), c = i % (D / 4), qi = qb * QBW + row;
+    if (qi >= q_len) continue;
+    u32x2 out = {0u, 0u};
+    if (kv_len > 0) {
+      const float m0 = w0[QBW * D + row], m1 = w1[QBW * D + row];
+      const float M = fmaxf(m0, m1);  // finite: the first half has a key
+      const float a0 = M - m0 > FLUSH_GAP ? 0.f : __builtin_amdgcn_exp2f(m0 - M);
+      const float a1 = M - m1 > FLUSH_GAP ? 0.f : __builtin_amdgcn_exp2f(m1 - M);  // m1 = -inf: an empty half
+      const float inv = 1.0f / (a0 * w0[QBW * D + QBW + row] + a1 * w1[QBW * D + QBW + row]);
+      const int off = ((c >> 2) * QBW + row) * 16 + 4 * (c & 3);
+      const f32x4 x0 = *(const f32x4*)(w0 + off), x1 = *(const f32x4*)(w1 + off);
+      const bf16x4 o4 = {f2bf((a0 * x0[0] + a1 * x1[0]) * inv), f2bf((a0 * x0[1] + a1 * x1[1]) * inv),
+                         f2bf((a0 * x0[2] + a1 * x1[2]) * inv), f2bf((a0 * x0[3] + a1 * x1[3]) * inv)};
+      out = __builtin_bit_cast(u32x2, o4);
+    }
+    const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
+    *(u32x2*)(a.o + (long)orow * a.os + h * D + 4 * c) = out;
   }
 }
 
@@ -507,14 +615,47 @@ extern "C" int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void
   if ((((uintptr_t)q) & 15) || (((uintptr_t)k) & 15) || (((uintptr_t)vt) & 15)) return SA_ERR_ARG;
   if ((((uintptr_t)q_scales) & 3) || (((uintptr_t)k_scales) & 3) || (((uintptr_t)vt_scales) & 3)) return SA_ERR_ARG;
   static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_TOTAL);
     return true;
   }();
   (void)attr;
   FwdArgs a{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
             (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o, o_stride, segs, vcol0, o_rows, heads};
-  hipLaunchKernelGGL(attn_fwd_mx_kernel, dim3((max_q_len + QBW - 1) / QBW, heads, nseg), dim3(512), LDS_TOTAL,
-                     (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_fwd_mx_kernel<false>, dim3((max_q_len + QBW - 1) / QBW, heads, nseg), dim3(512), LDS_TOTAL,
+                     (hipStream_t)stream, a, SplitArgs{});
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+extern "C" int sa_attn_fwd_mxfp8_split(const void* q, const void* q_scales, const void* k, const void* k_scales,
+                                       const void* vt, const void* vt_scales, int64_t Rv, void* o, int64_t o_stride,
+                                       const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len, int heads,
+                                       int head_dim, const int32_t* o_rows, int split_tiles, void* work,
+                                       int64_t work_bytes, void* stream) {
+  if (!q || !q_scales || !k || !k_scales || !vt || !vt_scales || !o || !segs || !vcol0 || !work) return SA_ERR_ARG;
+  if (nseg <= 0 || heads <= 0 || head_dim != D || max_q_len <= 0) return SA_ERR_ARG;
+  if (Rv <= 0 || Rv % KVB) return SA_ERR_ARG;
+  if (o_stride < (int64_t)heads * D || o_stride % 8 || (((uintptr_t)o) & 15)) return SA_ERR_ARG;
+  if ((((uintptr_t)q) & 15) || (((uintptr_t)k) & 15) || (((uintptr_t)vt) & 15)) return SA_ERR_ARG;
+  if ((((uintptr_t)q_scales) & 3) || (((uintptr_t)k_scales) & 3) || (((uintptr_t)vt_scales) & 3)) return SA_ERR_ARG;
+  const int nqb = (max_q_len + QBW - 1) / QBW;
+  const int64_t ntiles = (int64_t)nseg * heads * nqb;
+  if (split_tiles <= 0 || split_tiles > ntiles || ntiles + split_tiles > 0x7fffffff) return SA_ERR_ARG;
+  if ((((uintptr_t)work) & 15) || work_bytes < (int64_t)split_tiles * 2 * WBLK * 4) return SA_ERR_ARG;
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_TOTAL);
+    return true;
+  }();
+  (void)attr;
+  FwdArgs a{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
+            (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o, o_stride, segs, vcol0, o_rows, heads};
+  SplitArgs sp{nqb, (int)(ntiles - split_tiles), (float*)work};
+  hipLaunchKernelGGL(attn_fwd_mx_kernel<true>, dim3((unsigned)(ntiles + split_tiles)), dim3(512), LDS_TOTAL,
+                     (hipStream_t)stream, a, sp);
+  SA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_mx_split_merge_kernel, dim3(split_tiles), dim3(256), 0, (hipStream_t)stream, a, sp);
   SA_LAUNCH_CHECK();
   return SA_OK;
 }

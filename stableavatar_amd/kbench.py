@@ -4,7 +4,8 @@ Selectors: gemm, attn, gemmvar, attnvar, dit, ditvar, ...; gemmfp8 = the fp8 FFN
 against the bf16 kernels, ditfp8 = the whole forward with the mode off and on; attnfp8 = the config-2 self-attention
 launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the whole forward with that mode off, on, and
 on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (LayerNorm .. operands ready) in bf16, with the
-fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused."""
+fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused;
+attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16."""
 from __future__ import annotations
 
 import json
@@ -281,6 +282,8 @@ def main(which=("gemm", "attn")):
         print(json.dumps(res[-1]), flush=True)
     if "attnfp8" in which:  # the fp8 attention mode's kernels against the bf16 launch, interleaved rounds
         res.extend(bench_fp8_attn())
+    if "attnfp8split" in which:  # the key-split launch at the Ulysses N = 8 rank shape, fp8 and bf16, interleaved
+        res.extend(bench_fp8_attn_split())
     if "qkvfp8" in which:  # the fp8 q/k/v mode's operand chains against the bf16 one, interleaved rounds
         res.extend(bench_fp8_qkv())
     if "ditfp8qkv" in which:  # whole-forward A/B of enable_fp8_qkv() on top of the other two modes, interleaved
@@ -346,6 +349,76 @@ def bench_fp8_attn(L=21504, H=12, B=3):
         r[f"{n}_ms"] = round(ms[n], 4)
     r.update(ratio_total=round(ms["bf16"] / ms["fp8_total"], 3), ratio_kernel=round(ms["bf16"] / ms["fp8_kernel"], 3),
              bf16_tflops=round(fl / ms["bf16"] / 1e9, 1), fp8_kernel_tflops=round(fl / ms["fp8_kernel"] / 1e9, 1))
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
+def bench_fp8_attn_split(Lq=10752, Lk=21504, H=3, B=3, rounds=5):
+    """The Ulysses N = 8 rank's self-attention launch at config 2 (3 segments x 3 heads, 10 752 queries and 21 504 keys
+    each: 378 tiles), kernels alone on packed operands, same process, interleaved rounds, median of `rounds`: the
+    MXFP8 flash kernel unsplit and with ops.attn_tail_split's tail as key halves, the bf16 8-wave kernel likewise, and
+    the three per-row launches of the per-row-stream schedule on three streams, unsplit and with the last row's tail
+    split.  Every round's time is kept (`*_rounds_ms`): the spread between rounds of one arm is what a difference
+    between arms is read against.  ratio_* = unsplit ms / split ms (> 1: the split is faster)."""
+    dev, D = "cuda", 128
+    g = torch.Generator(device=dev).manual_seed(0)
+    q = torch.randn(B * Lq, H * D, device=dev, generator=g).bfloat16()
+    k, v = (torch.randn(B * Lk, H * D, device=dev, generator=g).bfloat16() for _ in range(2))
+    o, os_, o8, o8s, o8r = (torch.empty(B * Lq, H * D, device=dev, dtype=torch.bfloat16) for _ in range(5))
+    rows = [[b * Lq, Lq, b * Lk, Lk] for b in range(B)]
+    segs = torch.tensor(rows, dtype=torch.int32, device=dev)
+    vcol0, Rv = ops.attn_vcol0(rows)
+    vc = torch.tensor(vcol0, dtype=torch.int32, device=dev)
+    buf = ops.AttnMx8(B * Lq, B * Lk, H, Rv, B, dev)
+    ops.attn_pack_mxfp8(q, k, v, segs, vc, B, Lq, Lk, H, buf, kmean=ops.attn_kmean(k, segs, B, H, buf.kmean,
+                                                                                  buf.kmean_work))
+    n_row = H * -(-Lq // 256)
+    split = ops.attn_tail_split(0, B * n_row, q.device)
+    split_row = ops.attn_tail_split((B - 1) * n_row, n_row, q.device)
+    # the per-row launches: one segment table, one operand set (and one split scratch) per row, one stream per row
+    seg1 = torch.tensor([[0, Lq, 0, Lk]], dtype=torch.int32, device=dev)
+    vc1 = torch.zeros(1, dtype=torch.int32, device=dev)
+    bufs, streams = [], [torch.cuda.Stream() for _ in range(B)]
+    for b in range(B):
+        rb = ops.AttnMx8(Lq, Lk, H, ops.attn_vcol0(rows[:1])[1], 1, dev)
+        kb = k[b * Lk:(b + 1) * Lk]
+        ops.attn_pack_mxfp8(q[b * Lq:(b + 1) * Lq], kb, v[b * Lk:(b + 1) * Lk], seg1, vc1, 1, Lq, Lk, H, rb,
+                            kmean=ops.attn_kmean(kb, seg1, 1, H, rb.kmean, rb.kmean_work))
+        bufs.append(rb)
+
+    def per_row(out, st):
+        cur = torch.cuda.current_stream()
+        for b in range(B):
+            streams[b].wait_stream(cur)
+            with torch.cuda.stream(streams[b]):
+                ops.attn_fwd_mxfp8(bufs[b], out[b * Lq:(b + 1) * Lq], seg1, vc1, 1, Lq, H,
+                                   split_tiles=st if b == B - 1 else 0)
+        for s in streams:
+            cur.wait_stream(s)
+
+    fns = {"fp8": lambda: ops.attn_fwd_mxfp8(buf, o8, segs, vc, B, Lq, H),
+           "fp8_split": lambda: ops.attn_fwd_mxfp8(buf, o8s, segs, vc, B, Lq, H, split_tiles=split),
+           "bf16": lambda: ops.attention(q, k, v, o, segs, B, Lq, H, kernel=1),
+           "bf16_split": lambda: ops.attention(q, k, v, os_, segs, B, Lq, H, split_tiles=split),
+           "fp8_rows": lambda: per_row(o8, 0),
+           "fp8_rows_split": lambda: per_row(o8r, split_row)}
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(rounds):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=20, warmup=3))
+        clocks.append(_sclk_mhz())
+    ms = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
+    rel = lambda a, b: round(((a.float() - b.float()).norm() / b.float().norm()).item(), 6)  # noqa: E731
+    r = {"kernel": "fp8attn_split", "Lq": Lq, "Lk": Lk, "heads": H, "rows": B, "tiles": B * n_row,
+         "cus": ops._n_cu(q.device), "split_tiles": split, "split_tiles_last_row": split_row, "sclk_mhz": clocks,
+         "rel_l2_fp8_split_vs_fp8": rel(o8s, o8), "rel_l2_fp8_rows_split_vs_fp8": rel(o8r, o8),
+         "rel_l2_bf16_split_vs_bf16": rel(os_, o), "rel_l2_fp8_vs_bf16": rel(o8, o)}
+    for n in fns:
+        r[f"{n}_ms"] = round(ms[n], 4)
+        r[f"{n}_rounds_ms"] = [round(t, 4) for t in times[n]]
+        r[f"{n}_spread"] = round((max(times[n]) - min(times[n])) / ms[n], 4)
+    r.update(ratio_fp8=round(ms["fp8"] / ms["fp8_split"], 3), ratio_bf16=round(ms["bf16"] / ms["bf16_split"], 3),
+             ratio_fp8_rows=round(ms["fp8_rows"] / ms["fp8_rows_split"], 3))
     print(json.dumps(r), flush=True)
     return [r]
 

@@ -25,6 +25,9 @@ scale byte 127 - P_SHIFT.  The kernel keeps a running maximum that lags the true
 rescale), so its P^ reach 2^(P_SHIFT + LAG) <= 256 < 448.  o = (P^ V^) / sum(P^) with the sum over the rounded P in
 fp32: the weights sum to one whatever the rounding did, and a one-hot P returns its V row exactly.  kv_len == 0
 gives zeros.
+
+Key split (sa_attn_fwd_mxfp8_split): the last split_tiles (segment, head, 256-query block) tiles of a launch take their
+keys in two halves, each half the definition above on its own keys, merged by attend_split.
 """
 from __future__ import annotations
 
@@ -151,13 +154,68 @@ def attend(qd, kd, vd):
     return (ph @ vd) / ph.sum(-1, keepdim=True)
 
 
-def attention(q, k, v, segs, heads, scale=None, kmean=None, o_rows=None, out=None):
+QB = 256  # queries per tile of the key-split launch
+DROP_GAP = 10 + P_SHIFT  # exp2(-DROP_GAP) * 2^P_SHIFT = 2^-10 is the e4m3 rounding boundary: half the least subnormal
+
+
+def split_point(kv_len: int) -> int:
+    """kper: the first half of a split tile is keys [0, kper), whole 128-key blocks; the second the rest"""
+    return ceil128((kv_len + 1) // 2)
+
+
+def attend_half(qd, kd, vd):
+    """one key half by the definition on its own keys: (m its row maximum [.., L], O = P^ V^ unnormalised [.., L, 128],
+    l = sum P^ [.., L]), fp32"""
+    s = qd @ kd.transpose(-1, -2)
+    m = s.amax(-1)
+    ph = torch.ldexp(torch.exp2(s - m[..., None]), torch.tensor(P_SHIFT)).to(torch.float8_e4m3fn).float()
+    return m, ph @ vd, ph.sum(-1)
+
+
+def attend_split(qd, kd, vd):
+    """attend() with the keys in two halves at split_point, as sa_attn_fwd_mxfp8_split runs a split tile: each half is
+    the definition on its own keys (its own row maximum), merged with w_h = exp2(m_h - M), M = max(m_0, m_1):
+    o = (w_0 O_0 + w_1 O_1) / (w_0 l_0 + w_1 l_1).  A half whose maximum stands more than DROP_GAP below M gets
+    w_h = 0: each of its P, taken against the row's maximum as attend() takes it, rounds to zero (the flash loop's own
+    drop rule, FLUSH_GAP, across halves), so a one-hot P still returns its V row exactly.  An empty second half has
+    w = 0 and the result is attend()'s."""
+    kper = split_point(kd.shape[-2])
+    if kper >= kd.shape[-2]:
+        return attend(qd, kd, vd)
+    m0, O0, l0 = attend_half(qd, kd[..., :kper, :], vd[..., :kper, :])
+    m1, O1, l1 = attend_half(qd, kd[..., kper:, :], vd[..., kper:, :])
+    M = torch.maximum(m0, m1)
+    w0 = torch.where(M - m0 > DROP_GAP, torch.zeros_like(M), torch.exp2(m0 - M))[..., None]
+    w1 = torch.where(M - m1 > DROP_GAP, torch.zeros_like(M), torch.exp2(m1 - M))[..., None]
+    return (w0 * O0 + w1 * O1) / (w0 * l0[..., None] + w1 * l1[..., None])
+
+
+def split_mask(segs, heads, split_tiles, max_q_len=None):
+    """bool [nseg][heads, q_len]: the queries in the last split_tiles tiles of the launch.  Tile = (segment, head,
+    256-query block), numbered (seg * heads + h) * nqb + qb with nqb = ceil(max_q_len / 256) (sa_attn_fwd_split's
+    order); tiles that hold no query count."""
+    if max_q_len is None:
+        max_q_len = max(int(s[1]) for s in segs)
+    nqb = (max_q_len + QB - 1) // QB
+    ntiles = len(segs) * heads * nqb
+    if not 0 <= split_tiles <= ntiles:
+        raise ValueError(f"split_tiles = {split_tiles} of {ntiles} tiles")
+    out = []
+    for i, s in enumerate(segs):
+        tile = (i * heads + torch.arange(heads)[:, None]) * nqb + torch.arange(int(s[1]))[None, :] // QB
+        out.append(tile >= ntiles - split_tiles)
+    return out
+
+
+def attention(q, k, v, segs, heads, scale=None, kmean=None, o_rows=None, out=None, split_tiles=0, max_q_len=None):
     """The mode's self-attention over a segment table, row-major q, k, v [rows, heads * 128] -> bf16 [rows, heads * 128]
-    (row r's output at row o_rows[r] when given)."""
+    (row r's output at row o_rows[r] when given).  split_tiles > 0: the last split_tiles tiles of the launch
+    (split_mask; max_q_len as the launch is given it, default the longest segment) by attend_split."""
     if scale is None:
         scale = D ** -0.5
     if out is None:
         out = torch.zeros(q.shape[0], heads * D, dtype=torch.bfloat16)
+    mask = split_mask(segs, heads, split_tiles, max_q_len) if split_tiles else None
     for i, (q0, ql, k0, kl) in enumerate(segs):
         rows = torch.arange(q0, q0 + ql)
         if o_rows is not None:
@@ -169,6 +227,8 @@ def attention(q, k, v, segs, heads, scale=None, kmean=None, o_rows=None, out=Non
                                       None if kmean is None else kmean[i])
         h = lambda t: t.reshape(t.shape[0], heads, D).transpose(0, 1)  # noqa: E731
         o = attend(h(qd), h(kd), h(vd))
+        if mask is not None and mask[i].any():
+            o = torch.where(mask[i][..., None], attend_split(h(qd), h(kd), h(vd)), o)
         out[rows] = o.transpose(0, 1).reshape(ql, heads * D).bfloat16()
     return out
 

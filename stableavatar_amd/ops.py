@@ -120,7 +120,8 @@ ATTN_VT_P32 = 3
 
 
 def attn_tail_split(n_tiles_before, n_tiles, device):
-    """How many of a launch's (segment, head, 256-query block) tiles to run as two key halves (sa_attn_fwd_split):
+    """How many of a launch's (segment, head, 256-query block) tiles to run as two key halves (sa_attn_fwd_split, and
+    sa_attn_fwd_mxfp8_split in the fp8 attention mode):
     the tiles past the last full round over the CUs when that round is at most half full, counting n_tiles_before
     tiles of launches running concurrently ahead of this one (the per-CFG-row streams of the sequence-parallel
     schedule); 0 = no split.  SA_ATTN_SPLIT=0 disables it."""
@@ -277,7 +278,10 @@ KMEAN_SPLIT = 16  # sa_attn_kmean's row ranges per segment (its work buffer: nse
 class AttnMx8:
     """The operand buffers of attention_mxfp8 (stableavatar_amd/mxfp8_attn.py), allocated once by their owner: Q^ / K^
     bytes [rows, heads * 128] + scales [rows, heads * 4], V^T bytes [heads * 128, Rv] + scales [heads * 128, Rv / 32],
-    k_mean fp32 [nseg, heads * 128] and sa_attn_kmean's partial sums."""
+    k_mean fp32 [nseg, heads * 128] and sa_attn_kmean's partial sums; and the fp32 partials of the key-split launch
+    (sa_attn_fwd_mxfp8_split), allocated on first use and grown when a later call needs more.  One AttnMx8 serves one
+    launch at a time: concurrent launches (the per-row streams of the sequence-parallel schedule) each have their own,
+    so their halves never share scratch."""
 
     def __init__(self, q_rows, k_rows, heads, Rv, nseg, device):
         C = heads * 128
@@ -290,6 +294,14 @@ class AttnMx8:
         self.vq, self.vs = torch.empty(C, Rv, **u8), torch.empty(C, Rv // 32, **u8)
         self.kmean = torch.empty(nseg, C, device=device, dtype=torch.float32)
         self.kmean_work = torch.empty(nseg * KMEAN_SPLIT, C, device=device, dtype=torch.float32)
+        self.split_work = None
+
+    def work(self, split_tiles):
+        """fp32 scratch of the key-split launch: split_tiles * 2 * 256 * (128 + 2) floats"""
+        n = split_tiles * 2 * 256 * (128 + 2)
+        if self.split_work is None or self.split_work.numel() < n:
+            self.split_work = torch.empty(n, device=self.qq.device, dtype=torch.float32)
+        return self.split_work
 
 
 def attn_vcol0(seg_rows):
@@ -329,12 +341,21 @@ def attn_pack_mxfp8(q, k, v, segs, vcol0, nseg, max_q_len, max_kv_len, heads, bu
     return buf
 
 
-def attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows=None):
-    """the flash kernel on packed operands (sa_attn_fwd_mxfp8); out bf16 [rows, >= heads * 128]"""
+def attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows=None, split_tiles=0):
+    """the flash kernel on packed operands (sa_attn_fwd_mxfp8); out bf16 [rows, >= heads * 128]; split_tiles > 0: the
+    last split_tiles (segment, head, 256-query block) tiles as two key halves + a merge (sa_attn_fwd_mxfp8_split,
+    mxfp8_attn.attend_split), the partials in buf's scratch"""
     _check(out, torch.bfloat16, "attn_fwd_mxfp8.out")
     assert out.stride(-1) == 1 and buf.heads == heads
     if o_rows is not None:
         assert o_rows.dtype == torch.int32 and o_rows.is_cuda and o_rows.is_contiguous()
+    if split_tiles:
+        work = buf.work(int(split_tiles))
+        call("sa_attn_fwd_mxfp8_split", buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(),
+             buf.vq.data_ptr(), buf.vs.data_ptr(), buf.Rv, out.data_ptr(), out.stride(0), segs.data_ptr(),
+             vcol0.data_ptr(), nseg, max_q_len, heads, 128, _p(o_rows), int(split_tiles), work.data_ptr(),
+             work.numel() * 4, _stream())
+        return out
     call("sa_attn_fwd_mxfp8", buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(),
          buf.vq.data_ptr(), buf.vs.data_ptr(), buf.Rv, out.data_ptr(), out.stride(0), segs.data_ptr(),
          vcol0.data_ptr(), nseg, max_q_len, heads, 128, _p(o_rows), _stream())
@@ -342,15 +363,15 @@ def attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows=None):
 
 
 def attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv_len, buf, head_dim=128, scale=None,
-                    o_rows=None, k_mean=True):
+                    o_rows=None, k_mean=True, split_tiles=0):
     """Self-attention on MXFP8 operands (the fp8 attention mode; mxfp8_attn.py is the definition): the K column means
-    of each segment, the operand pack, the flash kernel.  q, k, v bf16 rows as attention(); vcol0: device int32 per
+    of each segment, the operand pack, the flash kernel (split_tiles as attn_fwd_mxfp8).  q, k, v bf16 rows as attention(); vcol0: device int32 per
     segment and max_kv_len from attn_vcol0's layout (buf.Rv its second result); buf: AttnMx8 owned by the caller."""
     if head_dim != 128:
         raise ValueError("attention_mxfp8: head_dim 128 only")
     km = attn_kmean(k, segs, nseg, heads, buf.kmean, buf.kmean_work) if k_mean else None
     attn_pack_mxfp8(q, k, v, segs, vcol0, nseg, max_q_len, max_kv_len, heads, buf, scale, km)
-    return attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows)
+    return attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows, split_tiles)
 
 
 def linear_mxfp8_vt(x, weight, bias, rows_per_seg, nseg, buf):

@@ -386,7 +386,9 @@ class WanTransformer3DFantasyModel(nn.Module):
 
     def _self_attn(self, ws, q, k, v, out, segs, nseg, max_q_len, heads, kernel=0, o_rows=None, split_tiles=0):
         """One self-attention launch of a DiT block: ops.attention, or with enable_fp8_attention() the K means, the
-        operand pack and the MXFP8 flash kernel (ops.attention_mxfp8; no key split there).  The operand buffers live
+        operand pack and the MXFP8 flash kernel (ops.attention_mxfp8); split_tiles (ops.attn_tail_split, given by the
+        sequence-parallel sites alone; in fp8 mode by the batched one alone, see _sp_layer_rows) goes to either.  The
+        operand buffers and the split's scratch live
         in the workspace, one set per segment table (the per-row streams of the sequence-parallel schedule run
         concurrently, each on its own table), allocated on first use."""
         if not self._fp8_attn:
@@ -397,7 +399,8 @@ class WanTransformer3DFantasyModel(nn.Module):
         buf = ws.attn8.get(key)
         if buf is None:
             buf = ws.attn8[key] = ops.AttnMx8(q.shape[0], k.shape[0], heads, Rv, nseg, q.device)
-        return ops.attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv, buf, o_rows=o_rows)
+        return ops.attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv, buf, o_rows=o_rows,
+                                   split_tiles=split_tiles)
 
     def enable_multi_gpus_inference(self, group=None, loopback=None):
         """Ulysses sequence parallelism over torch.distributed (RCCL); replaces the xfuser path
@@ -709,9 +712,12 @@ class WanTransformer3DFantasyModel(nn.Module):
         nv = n_fr * nper
         pend, back = [], []
         # the rows' attention launches run concurrently: the tiles past their last full round over the CUs (in the
-        # last row's launch) run as key halves (ops.attn_tail_split), all rows on the 8-wave kernel then
+        # last row's launch) run as key halves (ops.attn_tail_split), all rows on the 8-wave kernel then.  Not in
+        # the fp8 attention mode: there the three concurrent launches measured 3 % slower with the last row's tail
+        # split than without (profiles/r10/fp8_attn_split.jsonl), so its key split serves the batched launch alone
         n_row = hg * -(-Lq // 256)
-        splits = [ops.attn_tail_split(b * n_row, n_row, x.device) if self.attn_kernel == 0 else 0 for b in range(B)]
+        splits = [ops.attn_tail_split(b * n_row, n_row, x.device) if self.attn_kernel == 0 and not self._fp8_attn
+                  else 0 for b in range(B)]
         akern = 1 if any(splits) else self.attn_kernel
         for b, st in enumerate(rstreams if sa else []):  # self-attention inputs (1B:675-676) and the Q/K/V exchange
             rs = slice(b * Lc, (b + 1) * Lc)
