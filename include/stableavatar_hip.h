@@ -291,12 +291,15 @@ int sa_mod_add(const float* mod, const float* e, int64_t e_bstride, int64_t e_js
                int C, void* stream);
 
 /* CFG combine + FlowMatchEulerDiscreteScheduler.step + overlap blend + scatter of one window
- * (wan/pipeline/wan_inference_long_pipeline.py:751-779). */
+ * (wan/pipeline/wan_inference_long_pipeline.py:751-779).  Frames (start + f) % T; start >= 0, and prev_end >= overlap
+ * when blending (SA_ERR_ARG otherwise, as for any non-positive size of the entry points of this group). */
 int sa_flow_step(const void* latents_all, void* pred_all, const void* noise, int R, int C, int T, int Fw,
                  int64_t HW, int start, float dsigma, float audio_scale, float text_scale, int overlap, int prev_end,
                  const float* weights, int blend, void* stream);
 
-/* out[r] = idx[r] >= 0 ? in[idx[r]] : 0  (split_tensor_with_padding, vocal_projector_fantasy.py:81-131) */
+/* out[r] = idx[r] >= 0 ? in[idx[r]] : 0  (split_tensor_with_padding, vocal_projector_fantasy.py:81-131).
+ * nrows == 0 is a no-op that returns SA_OK (as n == 0 of sa_fill_f32 / sa_cast_f32_bf16); nrows < 0 or
+ * row_bytes <= 0 is SA_ERR_ARG. */
 int sa_gather_rows(const void* in, int64_t in_row_bytes, const int32_t* idx, int nrows, void* out,
                    int64_t out_row_bytes, int64_t row_bytes, void* stream);
 

@@ -111,13 +111,19 @@ __global__ void mod_add_kernel(const float* mod, const float* e, long eb, long e
 
 // One sampler step for one window (pipeline:751-779):
 //   v   = u + a*(d-u) + t*(c-d)                      (bf16 noise_pred rows u/d/c)   if cfg
-//   x1  = bf16( x0 + bf16((sigma_next - sigma) * v) )  (FlowMatchEuler step, sample upcast to fp32)
+//   x1  = bf16( x0 + bf16(bf16(sigma_next - sigma) * v) )  (FlowMatchEuler step, sample upcast to fp32; torch casts
+//         the 0-d fp32 step size to the bf16 of the tensor it multiplies)
 //   x1[j] = bf16( x1[j]*w_j + prev[j]*(1-w_j) )      for the first `overlap` frames when blending
 //   dst[frame_start + j] = x1[j]
 // Layout: latents [C, T, HW] (batch 1); noise_pred [R, C, Fw, HW]; window = frames [s, s+Fw).
 __global__ void flow_step_kernel(const bf16* latents_all, bf16* pred_all, const bf16* noise, int R, int C, int T,
                                  int Fw, long HW, int start, float dsigma, float audio_scale, float text_scale,
                                  int overlap, int prev_end, const float* wts, int blend) {
+  // every product and sum below is its own rounded bf16 op of the reference: no contraction.  Left on, the gfx950
+  // code for the blend has no conversion of x1 * w: a v_fmac_f32 adds the unrounded product to the rounded a2 (x1
+  // and w are bf16 values, so the narrowed product may be formed inside an fma), and the result is one bf16 place
+  // off torch's on a fifth of the blended elements; with the pragma the v_fmac is gone
+#pragma clang fp contract(off)
   const long n = (long)C * Fw * HW;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
@@ -138,7 +144,8 @@ __global__ void flow_step_kernel(const bf16* latents_all, bf16* pred_all, const 
   }
   const int fa = (start + f) % T;
   const float x0 = bf2f(latents_all[((long)c * T + fa) * HW + p]);
-  float x1 = bf2f(f2bf(x0 + bf2f(f2bf(dsigma * v))));  // 0-d fp32 * bf16 tensor -> bf16, then + fp32 sample
+  // 0-d fp32 * bf16 tensor -> bf16, the 0-d operand cast to bf16 first; then + fp32 sample
+  float x1 = bf2f(f2bf(x0 + bf2f(f2bf(bf2f(f2bf(dsigma)) * v))));
   if (blend && f < overlap) {
     const float w = bf2f(f2bf(wts[f]));
     const int fp = (prev_end - overlap + f) % T;
@@ -179,6 +186,7 @@ extern "C" int sa_patch_im2col(const void* x, int64_t xb, int64_t xc, int64_t xf
                                int64_t yc, int64_t yf, int ycn, int B, int F, int H, int W, void* out, int Kpad,
                                int Lpad, void* stream) {
   if (!x || !out || Kpad % 8 || Kpad < 4 * (xcn + ycn) || H % 2 || W % 2) return SA_ERR_ARG;
+  if (B <= 0 || F <= 0 || H <= 0 || W <= 0 || Kpad <= 0 || Lpad <= 0 || xcn <= 0 || ycn < 0) return SA_ERR_ARG;
   if (ycn > 0 && !y) return SA_ERR_ARG;
   if ((long)F * (H / 2) * (W / 2) > Lpad) return SA_ERR_ARG;
   const long n = (long)B * Lpad * (Kpad / 8);
@@ -191,6 +199,7 @@ extern "C" int sa_patch_im2col(const void* x, int64_t xb, int64_t xc, int64_t xf
 extern "C" int sa_unpatchify(const void* in, int64_t ld_in, int Lpad, int B, int C, int F, int H, int W, void* out,
                              int out_dtype, void* stream) {
   if (!in || !out || H % 2 || W % 2) return SA_ERR_ARG;
+  if (B <= 0 || C <= 0 || F <= 0 || H <= 0 || W <= 0 || Lpad <= 0) return SA_ERR_ARG;
   const long n = (long)B * C * F * H * W;
   if (out_dtype == 1)
     hipLaunchKernelGGL(unpatchify_kernel<bf16>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -203,7 +212,7 @@ extern "C" int sa_unpatchify(const void* in, int64_t ld_in, int Lpad, int B, int
 }
 
 extern "C" int sa_timestep_embed(const float* t, int B, int dim, float* out, void* stream) {
-  if (!t || !out || dim % 2 || dim > 2048) return SA_ERR_ARG;
+  if (!t || !out || B <= 0 || dim <= 0 || dim % 2 || dim > 2048) return SA_ERR_ARG;
   hipLaunchKernelGGL(timestep_embed_kernel, dim3(B), dim3(dim / 2), 0, (hipStream_t)stream, t, B, dim, out);
   SA_LAUNCH_CHECK();
   return SA_OK;
@@ -211,7 +220,7 @@ extern "C" int sa_timestep_embed(const float* t, int B, int dim, float* out, voi
 
 extern "C" int sa_small_linear_f32(const float* in, int64_t ldi, int M, const void* W, int64_t ldw, const float* bias,
                                    float* out, int64_t ldo, int N, int K, int act_in, int act_out, void* stream) {
-  if (!in || !W || !out || M <= 0 || M > 8 || K % 8 || ldw % 8) return SA_ERR_ARG;
+  if (!in || !W || !out || M <= 0 || M > 8 || N <= 0 || K <= 0 || K % 8 || ldw % 8) return SA_ERR_ARG;
   hipLaunchKernelGGL(small_linear_kernel, dim3(nblk(N, 4)), dim3(256), 0, (hipStream_t)stream, in, ldi, M,
                      (const bf16*)W, ldw, bias, out, ldo, N, K, act_in, act_out);
   SA_LAUNCH_CHECK();
@@ -220,7 +229,7 @@ extern "C" int sa_small_linear_f32(const float* in, int64_t ldi, int M, const vo
 
 extern "C" int sa_mod_add(const float* mod, const float* e, int64_t e_bstride, int64_t e_jstride, float* out, int L,
                           int B, int J, int C, void* stream) {
-  if (!mod || !e || !out) return SA_ERR_ARG;
+  if (!mod || !e || !out || L <= 0 || B <= 0 || J <= 0 || C <= 0) return SA_ERR_ARG;
   const long n = (long)L * B * J * C;
   hipLaunchKernelGGL(mod_add_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, mod, e, e_bstride, e_jstride,
                      out, L, B, J, C);
@@ -232,7 +241,8 @@ extern "C" int sa_flow_step(const void* latents_all, void* pred_all, const void*
                             int64_t HW, int start, float dsigma, float audio_scale, float text_scale, int overlap,
                             int prev_end, const float* weights, int blend, void* stream) {
   if (!latents_all || !pred_all || !noise || (R != 1 && R != 3) || Fw > T) return SA_ERR_ARG;
-  if (blend && (!weights || overlap <= 0 || overlap > Fw)) return SA_ERR_ARG;
+  if (C <= 0 || T <= 0 || Fw <= 0 || HW <= 0 || start < 0) return SA_ERR_ARG;
+  if (blend && (!weights || overlap <= 0 || overlap > Fw || prev_end < overlap)) return SA_ERR_ARG;
   const long n = (long)C * Fw * HW;
   hipLaunchKernelGGL(flow_step_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)latents_all, (bf16*)pred_all, (const bf16*)noise, R, C, T, Fw, HW, start, dsigma,
@@ -244,6 +254,8 @@ extern "C" int sa_flow_step(const void* latents_all, void* pred_all, const void*
 extern "C" int sa_gather_rows(const void* in, int64_t in_row_bytes, const int32_t* idx, int nrows, void* out,
                               int64_t out_row_bytes, int64_t row_bytes, void* stream) {
   if (!in || !out || !idx || row_bytes % 4 || in_row_bytes % 4 || out_row_bytes % 4) return SA_ERR_ARG;
+  if (nrows < 0 || row_bytes <= 0) return SA_ERR_ARG;
+  if (nrows == 0) return SA_OK;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, (const char*)in,
                      in_row_bytes, idx, nrows, (char*)out, out_row_bytes, row_bytes);
   SA_LAUNCH_CHECK();

@@ -527,6 +527,10 @@ inline int ln_shared_rows() {
   return e ? atoi(e) : SA_LN_SHARED_DEFAULT;
 }
 
+// SA_QK_GENERIC (set to anything): the q/k launchers take qk_rmsnorm_rope_kernel / the unpaired pack where they would
+// take the pair kernels (read per call, for the A/B; the three launchers share it so that they choose alike)
+inline bool qk_generic() { return getenv("SA_QK_GENERIC") != nullptr; }
+
 template <typename TI, typename TO>
 int launch_ln(const LnArgs& a, hipStream_t st) {
   const int nw = ln_shared_rows();
@@ -600,7 +604,7 @@ extern "C" int sa_qk_rmsnorm_rope(void* x, int64_t ldx, int q_col, int k_col, co
   if (rope && (rows_per_batch <= 0 || head_dim % 8 || F <= 0 || H <= 0 || W <= 0)) return SA_ERR_ARG;
   QkArgs a{(bf16*)x, ldx, q_col, k_col, wq, wk, M, C, head_dim, eps, rope, rows_per_batch > 0 ? rows_per_batch : 1,
            tok_offset, F, H, W, n_frame_pairs, n_height_pairs};
-  static const bool generic = getenv("SA_QK_GENERIC") != nullptr;  // A/B switch, read once
+  const bool generic = qk_generic();
   if (rope && k_col >= 0 && C == 1536 && head_dim == 128 && !generic)
     hipLaunchKernelGGL(qk_rmsnorm_rope_pair_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   else if (C == 1536)
@@ -627,7 +631,7 @@ extern "C" int sa_qk_rmsnorm_rope_mxfp8(void* x, int64_t ldx, int q_col, int k_c
                     rows_per_batch > 0 ? rows_per_batch : 1, tok_offset, F, H, W, n_frame_pairs, n_height_pairs},
              (uint8_t*)q_out, ldq, (uint8_t*)q_scales, ldqs, scale * 1.4426950408889634f};
   // the kernel choice is sa_qk_rmsnorm_rope's, so that the values quantised are the ones it would have stored
-  static const bool generic = getenv("SA_QK_GENERIC") != nullptr;
+  const bool generic = qk_generic();
   hipStream_t st = (hipStream_t)stream;
   if (rope && k_col >= 0 && C == 1536 && !generic)
     hipLaunchKernelGGL(qk_rmsnorm_rope_pair_mx_kernel, dim3((M + 3) / 4), dim3(256), 0, st, m);
@@ -653,7 +657,7 @@ extern "C" int sa_qkv_pack(const void* x, int64_t ldx, const float* wq, const fl
   PackArgs pa{QkArgs{(bf16*)x, ldx, 0, C, wq, wk, M, C, head_dim, eps, rope, rows_per_batch, tok_offset, F, H, W,
                      n_frame_pairs, n_height_pairs},
               (const long*)table, G, R, my_part, b_offset};
-  static const bool generic = getenv("SA_QK_GENERIC") != nullptr;  // the in-place launcher's A/B switch
+  const bool generic = qk_generic();  // the in-place launcher's A/B switch
   if (C == 1536 && !generic)
     hipLaunchKernelGGL((qkv_pack_kernel<3, true>), dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, pa);
   else if (C == 1536)
