@@ -75,7 +75,18 @@ int sa_gemm_panel_slack_rows(void);
  * q_lens/k_lens ignored) for head_dim 128.  Rows of q/k/v/o are flat [rows, stride] bf16 matrices,
  * head h at column h*head_dim.  segs = device int32 [nseg][4] = {q_row0, q_len, kv_row0, kv_len}:
  * every query row of a segment attends to the kv_len rows starting at kv_row0 (this expresses the
- * batch dimension and the per-frame vocal grouping of :575-586).  accumulate != 0 adds into o. */
+ * batch dimension and the per-frame vocal grouping of :575-586).  accumulate != 0 adds into o.
+ * Segments may come in any order, leave gaps and share key ranges; kv_len == 0 writes zeros (adds nothing).
+ * Numerical contract (tests/attn_ref.py is the definition; every kernel id, sa_attn_fwd_split and sa_attn_cross3):
+ *   c = fp32(scale) * fp32(log2 e);  Q' = bf16(fp32(Q) * c);  S = Q' K^T accumulated in fp32;
+ *   P = bf16(exp2(S - m));  l = the sum of the rounded P;  O = (P V) / l accumulated in fp32 and rounded to bf16
+ *   once;  accumulate: o = bf16(fp32(o) + fp32(bf16(O))), one rounding per addition.
+ * The running max m moves lazily and is no part of the contract: after a move it stands 7 log2 units above the row's
+ * maximum (P <= 2^-7), and it moves again when some rounded P reaches 2, i.e. a score passes the maximum at the last
+ * move by 8 or more; O and l are rescaled by exp2 of the move, which is exact where the scores are integers.  A result
+ * is within 1 bf16 ulp of the fp64 softmax attention on (Q', K, V) plus 2^-20 of the softmax-weighted mean of |V|
+ * (half an ulp is the final rounding; the rest covers the fp32 sums and the reciprocal) wherever P is exact, and within
+ * 1.5 times the definition's own error otherwise (tests/test_gpu_attention_exact.py). */
 int sa_attn_fwd(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int nseg, int max_q_len,
                 int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride,
                 float scale, int accumulate, void* stream);
@@ -99,7 +110,10 @@ int sa_attn_fwd_map(const void* q, const void* k, const void* v, void* o, const 
  * split in two halves, each half a workgroup of its own writing fp32 partials (unnormalised O, running max, row sum)
  * to work, and a second launch merging them (log-sum-exp) into o.  For launches whose last round over the CUs is at
  * most half full (the Ulysses N = 8 per-rank shape: 378 tiles on 256 CUs -> the last 122 as 244 halves: 1.5 rounds
- * instead of 2).  work: >= split_tiles * 2 * 256 * (head_dim + 2) floats, 16-B aligned. */
+ * instead of 2).  work: >= split_tiles * 2 * 256 * (head_dim + 2) floats, 16-B aligned.
+ * The halves meet at key ceil64(ceil(kv_len / 2)); o = (w0 O0 + w1 O1) / (w0 l0 + w1 l1), w_h = exp2(m_h - max(m0, m1))
+ * in fp32, rounded to bf16 once (sa_attn_fwd's contract; the rows of whole tiles are the unsplit kernel's bytes).  An
+ * empty half weighs 0, and a split tile of a segment with kv_len == 0 writes zeros. */
 int sa_attn_fwd_split(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int nseg,
                       int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                       int64_t o_stride, float scale, int accumulate, const int32_t* o_rows, int split_tiles, void* work,
@@ -110,7 +124,10 @@ int sa_attn_fwd_split(const void* q, const void* k, const void* v, void* o, cons
  * and the vocal rows of their latent frame, [(b*n_frames + f)*nper, +nper) with
  * f = (tok_offset + i) / tokens_per_frame (1B:575-586 on the unsharded sequence); the outputs are
  * summed as bf16((bf16(text) + bf16(img))) + bf16(vocal) (1B:602) into o.  head_dim 128;
- * tokens_per_frame and tok_offset multiples of 256. */
+ * tokens_per_frame and tok_offset multiples of 256.
+ * Each source follows sa_attn_fwd's numerical contract with a softmax of its own (Q' is formed once); its running max
+ * sits on the row's maximum and moves when a score passes it by more than 8 (P <= 2^8 between moves).  Each source's
+ * output is rounded to bf16, and each of the two additions rounds to bf16 once. */
 int sa_attn_cross3(const void* q, int64_t q_stride, const void* kt, const void* vt, int64_t t_stride, int t_len,
                    const void* ki, const void* vi, int64_t i_stride, int i_len, const void* kv, const void* vv,
                    int64_t v_stride, int nper, int tokens_per_frame, int n_frames, int tok_offset, void* o,
@@ -119,7 +136,12 @@ int sa_attn_cross3(const void* q, int64_t q_stride, const void* kt, const void* 
 /* attention for head dims other than 128 and few queries per segment (vocal projector D=192,
  * vocal_projector_fantasy_1B.py:259-270; 14B :254-267, D = 640; wav2vec2 D = 64): fp32 softmax and math.
  * head_dim <= 256 (multiple of 8): any kv_len (keys in 64-key chunks, online softmax); 256 < head_dim <= 640:
- * exact softmax, kv_len <= 4096. */
+ * exact softmax, kv_len <= 4096.
+ * Numerical contract (tests/attn_ref.py, attention_small): sa_attn_fwd's with Q' = fp32(Q) * c and P kept in fp32 --
+ * neither is rounded to bf16 -- the running max on the row's maximum, O = (P V) / l in fp32 rounded to bf16 once; the
+ * key split merges fp32 partials by exp2(m_s - max m) before that rounding.  The one-wave-per-query kernel (head_dim
+ * > 256, or q / v / o not aligned for the tiled kernel) multiplies by fp32(scale) and uses exp, equal to that within
+ * fp32 rounding.  kv_len == 0 writes zeros. */
 int sa_attn_small(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int nseg, int max_q_len,
                   int max_kv_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                   int64_t o_stride, float scale, void* stream);

@@ -1430,7 +1430,8 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a) {
     const float M = fmaxf(m0, m1);
     const float a0 = m0 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m0 - M);
     const float a1 = m1 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m1 - M);
-    const float inv = 1.0f / (a0 * w0[QB * D + QB + row] + a1 * w1[QB * D + QB + row]);
+    const float l = a0 * w0[QB * D + QB + row] + a1 * w1[QB * D + QB + row];
+    const float inv = l > 0.f ? 1.0f / l : 0.f;  // a segment with no keys (both halves empty): zeros, as SDPA
     const f32x4 x0 = *(const f32x4*)(w0 + row * D + d), x1 = *(const f32x4*)(w1 + row * D + d);
     const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
     bf16* p = a.o + (long)orow * a.os + h * D + d;
