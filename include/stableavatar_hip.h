@@ -194,6 +194,19 @@ int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas
                   int64_t ldcs, int M, int N, int K, int epilogue, const float* residual, int64_t ldr,
                   const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream);
 
+/* sa_gemm_mxfp8 with the kernel chosen by the caller; every output and scale byte is the same under either kernel.
+ * kernel: 0 = auto (the one-tile kernel; the environment variable SA_MXGEMM_KERNEL=1|2, read once per process,
+ * overrides auto only), 1 = one 256x256 tile per workgroup, 2 = persistent: min(tiles, workgroups) workgroups, each
+ * walking tiles w, w + grid, ... and loading its next tile's first K-tile under the current tile's epilogue; any
+ * other value is rejected.  workgroups (kernel 2 only): 0 = one per CU of the current device, > 0 = a cap on the
+ * grid, a measurement and test hook like sa_attn_fwd_ex's kernel codes; < 0 is rejected.  sa_gemm_mxfp8 is this call
+ * with kernel = 0, workgroups = 0.  Every argument is checked before the first HIP call. */
+int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                     const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc, void* C_scales,
+                     int64_t ldcs, int M, int N, int K, int epilogue, const float* residual, int64_t ldr,
+                     const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel, int workgroups,
+                     void* stream);
+
 /* ---- MXFP8 self-attention (opt-in fp8 attention mode; no counterpart in the reference) ----
  * WanSelfAttention's attention (wan_fantasy_transformer3d_1B.py:383-413) with both products on MXFP8 operands.
  * stableavatar_amd/mxfp8_attn.py is the definition.  head_dim 128 only.  segs is sa_attn_fwd's table

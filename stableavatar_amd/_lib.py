@@ -27,7 +27,8 @@ SIGNATURES = {
     "sa_mxfp8_quant": "plplpliip",
     "sa_layernorm_mod_mxfp8": "pliplplppppliiifp",
     "sa_gemm_mxfp8": "plplplplpplpliiiiplplip",
-    "sa_attn_kmean": "plpiiippp",
+    "sa_gemm_mxfp8_ex": "plplplplpplpliiiiplpliiip",
+    "sa_attn_kmean":"plpiiippp",
     "sa_attn_pack_mxfp8": "plplplppiiiiifppppppplp",
     "sa_attn_fwd_mxfp8": "pppppplplppiiiipp",
     "sa_attn_fwd_mxfp8_split": "pppppplplppiiiipiplp",

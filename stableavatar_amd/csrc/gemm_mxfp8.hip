@@ -15,6 +15,8 @@
 // four (the 16-byte chunks g and 4 + g of the row -- the bf16 kernels' fragment addresses), and byte 0 of its scale
 // operand is the E8M0 scale of K block g (bytes 32 g .. 32 g + 31) of row r.  Operands are swapped (C^T = W·A^T) so
 // each lane holds 4 consecutive output columns of one row.
+// gemm_mxp_kernel (sa_gemm_mxfp8_ex, kernel 2): the same tile and K step, one workgroup walking several tiles and
+// loading its next tile's first K-tile under the current tile's epilogue; the same bytes (its header, below).
 //
 // sa_gemm_mxfp8_vt (the V projection of the fp8 q/k/v mode, feeding sa_attn_fwd_mxfp8): the same K loop with the
 // operands NOT swapped (C = A·W^T; the product of two operand rows does not depend on which side they sit, so the
@@ -26,6 +28,8 @@
 // one 16-byte store -- and the 32-position quantisation block 2 hi + g / 2 is this lane's 16 values and those of the
 // lane 16 further (g ^ 1): one shfl_xor for its amax.
 // Also here: sa_mxfp8_quant, the bf16 -> MXFP8 quantiser (weights at pack time; the definition's GPU twin).
+#include <stdlib.h>
+
 #include <utility>
 
 #include "mxfp8.h"
@@ -352,6 +356,256 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
   }
 }
 
+// gemm_mxp_kernel's row epilogue for the tile at (m0, n0): gemm_mx_kernel's, statement for statement (a copy: sharing
+// one function between the two kernels rescheduled gemm_mx_kernel's scalar prologue, DESIGN.md "Persistent MXFP8 GEMM").
+// acc[m][n] of lane (fr, fc) = row m0 + wm*128 + m*16 + fr, columns n0 + wn*128 + n*16 + 4 fc + 0..3, walked in column
+// pairs (n = 2p, 2p + 1): the 32 columns of pair p in one row are one MXFP8 block, held by lanes fr, fr + 16, + 32, + 48.
+template <int EPI>
+__device__ __forceinline__ void mxp_epilogue(const MxArgs& g, f32x4 (&acc)[8][8], int m0, int n0, int wm, int wn,
+                                             int fr, int fc) {
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    // pair p's accumulators leave the AGPRs here, after pair p - 1's stores: read all at once (the compiler's choice
+    // when left free) the 256 of them fill the VGPR file and the gated-residual and MXFP8 epilogues spill
+#pragma unroll
+    for (int m = 0; m < 8; ++m) asm volatile("" : "+a"(acc[m][2 * p]), "+a"(acc[m][2 * p + 1])::"memory");
+    const int cb = n0 + wn * 128 + p * 32;  // the block's first column (wave-uniform)
+    if (cb >= g.N) continue;
+    const int c[2] = {cb + 4 * fc, cb + 16 + 4 * fc};
+    float bv[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bv[h][e] = (g.bias && c[h] + e < g.N) ? g.bias[c[h] + e] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int row = m0 + wm * 128 + m * 16 + fr;
+      const bool live = row < g.M;
+      float v[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[4 * h + e] = acc[m][2 * p + h][e] + bv[h][e];
+      if constexpr (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MXFP8) {
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+          const bf16x2 hb = __builtin_convertvector((f32x2){v[j], v[j + 1]}, bf16x2);
+          const f32x2 y = gelu_tanh2(__builtin_convertvector(hb, f32x2));
+          v[j] = y[0];
+          v[j + 1] = y[1];
+        }
+      }
+      if constexpr (EPI == EPI_GELU_MXFP8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(v[j]));
+        float amax = mx_amax8(v);
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        uint32_t s;
+        const u32x2 q = mx_quant8(v, amax, &s);
+        if (live) {
+          uint8_t* C = (uint8_t*)g.C + (long)row * g.ldc;
+          *(uint32_t*)(C + c[0]) = q[0];
+          *(uint32_t*)(C + c[1]) = q[1];
+          if (fc == 0) g.SC[(long)row * g.ldsc + cb / 32] = (uint8_t)s;
+        }
+      } else if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_BF16) {
+        if (live) {
+          bf16* C = (bf16*)g.C + (long)row * g.ldc;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (c[h] + 4 <= g.N) {
+              *(bf16x4*)(C + c[h]) = (bf16x4){f2bf(v[4 * h]), f2bf(v[4 * h + 1]), f2bf(v[4 * h + 2]), f2bf(v[4 * h + 3])};
+            } else {
+              for (int e = 0; e < 4; ++e)
+                if (c[h] + e < g.N) C[c[h] + e] = f2bf(v[4 * h + e]);
+            }
+          }
+        }
+      } else {
+        if (live) {
+          float* C = (float*)g.C + (long)row * g.ldc;
+          const float* R = EPI == EPI_RES_F32 ? g.R + (long)row * g.ldr : nullptr;
+          const float* gt =
+              (EPI == EPI_RES_F32 && g.gate) ? g.gate + (long)(row / g.rows_per_batch) * g.gate_bstride : nullptr;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (c[h] + 4 <= g.N) {
+              f32x4 o = {v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
+              if constexpr (EPI == EPI_RES_F32) {
+                const f32x4 r = *(const f32x4*)(R + c[h]);
+                const f32x4 gg = gt ? *(const f32x4*)(gt + c[h]) : (f32x4){1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = r[e] + bf2f(f2bf(o[e])) * gg[e];
+              }
+              *(f32x4*)(C + c[h]) = o;
+            } else {
+              for (int e = 0; e < 4; ++e)
+                if (c[h] + e < g.N) {
+                  float o = v[4 * h + e];
+                  if constexpr (EPI == EPI_RES_F32) o = R[c[h] + e] + bf2f(f2bf(o)) * (gt ? gt[c[h] + e] : 1.0f);
+                  C[c[h] + e] = o;
+                }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// gemm_mxp_kernel: gemm_mx_kernel's tile, lane map, staging and K step, persistent over tiles.  Workgroup w of a grid of
+// G = min(tiles, workgroups) walks tiles w, w + G, ... of the xcd_remap / tile_coords order.  One running K-step counter
+// s gives the ring stage (s & 1), so a tile with an odd K-tile count hands the next tile the other stage.  During a
+// tile's last K step the free stage receives K-tile 0 (and its scales) of the workgroup's next tile, from load offsets
+// worked out in that step; those loads fly under the epilogue and the next tile's first step waits for them as any step
+// waits for its tile.  Each accumulator still adds K-tiles 0 .. nk - 1 in order, one MFMA each, so every output byte
+// equals gemm_mx_kernel's.
+// Barriers: one per K step, under tile- and step-loop bounds that depend on blockIdx.x, gridDim.x and the tile count
+// only; a workgroup without a tile returns before the first.
+struct MxpOff {
+  int g[4][4], sa, sw;  // a tile's 16 operand pieces and 2 scale rows per thread: byte offsets of K-tile 0
+};
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN, total = nm * nn;
+  const int nk = g.K / BKB;
+  const int G = gridDim.x;
+  if ((int)blockIdx.x >= total) return;
+
+  // the load offsets of tile u (gemm_mx_kernel's staging: rows past M / N clamped to the last row)
+  auto place = [&](int u, int tid, MxpOff& o, int& m0, int& n0) {
+    const int lane = tid & 63;
+    int mt, nt;
+    tile_coords(xcd_remap(u, total), nm, nn, g.group_m, mt, nt);
+    m0 = mt * BM;
+    n0 = nt * BN;
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = (i * 4 + wave) * 8 + (lane >> 3);
+        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+        if (h < 2)
+          o.g[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
+        else
+          o.g[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
+      }
+    o.sa = min(m0 + tid, g.M - 1) * (int)g.ldsa;
+    o.sw = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+  };
+  // K-tile kt of the placed tile and its scale dwords into ring stage st
+  auto issue = [&](const MxpOff& o, int kt, int st) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + o.g[h][i] + (long)kt * BKB),
+                                         LDS_PTR(smem + st * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024), 16,
+                                         0, 0);
+    char* dst = smem + LDS_BYTES + st * SCALE_STAGE + wave * 256;
+    __builtin_amdgcn_global_load_lds((const void*)(g.SA + o.sa + kt * 4), LDS_PTR(dst), 4, 0, 0);
+    __builtin_amdgcn_global_load_lds((const void*)(g.SW + o.sw + kt * 4), LDS_PTR(dst + 1024), 4, 0, 0);
+  };
+
+  f32x4 acc[8][8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  {
+    MxpOff first;
+    int m0, n0;
+    place(blockIdx.x, threadIdx.x, first, m0, n0);
+    issue(first, 0, 0);
+  }
+  int s = 0;  // K steps this workgroup has run, over all its tiles
+  for (int u = blockIdx.x; u < total; u += G) {
+    // Everything per lane is derived again, tile by tile, from a thread id the compiler cannot see through: nothing
+    // but the accumulators is then live across the epilogue, which needs most of the VGPR file (kept live across it,
+    // the fragment addresses and load offsets spilled)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, fr = lane & 15, fc = lane >> 4;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
+    const uint32_t swz = (fr >> 1) & 7;
+    const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
+    const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
+    const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
+    const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
+    const int sh = 8 * fc;
+    MxpOff cur;
+    int m0, n0;
+    place(u, tid, cur, m0, n0);
+    for (int t = 0; t < nk; ++t, ++s) {
+      // step s's tile has landed, and every wave is done reading the other stage (step s - 1, of this tile or of the
+      // workgroup's previous one), which the loads below overwrite
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      if (t + 1 < nk) {
+        issue(cur, t + 1, (s + 1) & 1);
+      } else if (u + G < total) {
+        // the next tile's offsets live in this branch only: replacing `cur` here makes every step of the loop copy
+        // and sign-extend all 18 of them (measured: 4 % on a 70-step tile); the next tile derives them again
+        MxpOff nxt;
+        int nm0, nn0;
+        place(u + G, tid, nxt, nm0, nn0);
+        issue(nxt, 0, (s + 1) & 1);
+      }
+      const uint32_t so = (s & 1) * STAGE_BYTES, ss = (s & 1) * SCALE_STAGE;
+      u32x4 bl[8], bh[8], al[2], ah[2];
+      uint32_t sar[8], swr[8];
+      unroll<8>([&](auto n) {
+        mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
+        mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
+        mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
+        mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
+      });
+      mx_ds<0>(al[0], a_lo + so);
+      mx_ds<0>(ah[0], a_hi + so);
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
+                     "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
+                     "+v"(al[0]), "+v"(ah[0])::"memory");
+      asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
+                        "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
+                        "+v"(swr[6]), "+v"(swr[7]));
+      i32x8 b[8];
+      int sa[8], sw[8];
+#pragma unroll
+      for (int n = 0; n < 8; ++n) {
+        b[n] = mx_join(bl[n], bh[n]);
+        sa[n] = (int)(sar[n] >> sh);
+        sw[n] = (int)(swr[n] >> sh);
+      }
+      unroll<8>([&](auto mc) {
+        constexpr int m = mc.value;
+        if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
+        if constexpr (m < 7) {
+          mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
+          mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
+        }
+        const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
+#pragma unroll
+        for (int n = 0; n < 8; ++n) mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
+      });
+    }
+    // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    mxp_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+}
+
 template <int EPI>
 int launch(const MxArgs& g, hipStream_t st) {
   static const bool attr = [] {
@@ -363,6 +617,56 @@ int launch(const MxArgs& g, hipStream_t st) {
   hipLaunchKernelGGL((gemm_mx_kernel<EPI>), dim3(nm * nn), dim3(256), LDS_TOTAL, st, g);
   SA_LAUNCH_CHECK();
   return SA_OK;
+}
+
+enum { KERNEL_AUTO = 0, KERNEL_ONE_TILE = 1, KERNEL_PERSISTENT = 2 };
+// what auto resolves to (DESIGN.md "Persistent MXFP8 GEMM", Decision); the two kernels are bit-identical
+#ifndef SA_MXGEMM_KERNEL_DEFAULT
+#define SA_MXGEMM_KERNEL_DEFAULT KERNEL_ONE_TILE
+#endif
+
+// the kernel auto picks (SA_MXGEMM_KERNEL=1|2 overrides, read once per process)
+int env_kernel() {
+  static const int k = [] {
+    const char* e = getenv("SA_MXGEMM_KERNEL");
+    const int v = e ? atoi(e) : 0;
+    return (v == KERNEL_ONE_TILE || v == KERNEL_PERSISTENT) ? v : SA_MXGEMM_KERNEL_DEFAULT;
+  }();
+  return k;
+}
+
+int num_cus() {
+  // per device: the persistent grid is one workgroup per CU
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!cus[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+// workgroups: 0 = one per CU, > 0 = the cap on the grid (tests and A/B)
+template <int EPI>
+int launch_persistent(const MxArgs& g, int workgroups, hipStream_t st) {
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)gemm_mxp_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    return true;
+  }();
+  (void)attr;
+  const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  const int grid = min(tiles, workgroups > 0 ? workgroups : num_cus());
+  hipLaunchKernelGGL((gemm_mxp_kernel<EPI>), dim3(grid), dim3(256), LDS_TOTAL, st, g);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+template <int EPI>
+int launch_sel(const MxArgs& g, int kernel, int workgroups, hipStream_t st) {
+  if (kernel == KERNEL_AUTO) kernel = env_kernel();
+  return kernel == KERNEL_PERSISTENT ? launch_persistent<EPI>(g, workgroups, st) : launch<EPI>(g, st);
 }
 
 struct QuantArgs {
@@ -406,10 +710,12 @@ extern "C" int sa_mxfp8_quant(const void* x, int64_t ldx, void* q, int64_t ldq, 
   return SA_OK;
 }
 
-extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
-                             const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
-                             void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
-                             int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream) {
+extern "C" int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,
+                                int64_t ldw, const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
+                                void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
+                                int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel,
+                                int workgroups, void* stream) {
+  if (kernel < KERNEL_AUTO || kernel > KERNEL_PERSISTENT || workgroups < 0) return SA_ERR_ARG;
   if (!A || !A_scales || !W || !W_scales || !C || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
   if (K % BKB != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 || ldws < K / 32)
     return SA_ERR_ARG;
@@ -430,13 +736,21 @@ extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, i
            rows_per_batch > 0 ? rows_per_batch : 1, M, N, K, epilogue == EPI_RES_F32 ? 4 : 8, M, 0};
   hipStream_t st = (hipStream_t)stream;
   switch (epilogue) {
-    case EPI_BF16: return launch<EPI_BF16>(g, st);
-    case EPI_GELU_BF16: return launch<EPI_GELU_BF16>(g, st);
-    case EPI_F32: return launch<EPI_F32>(g, st);
-    case EPI_RES_F32: return launch<EPI_RES_F32>(g, st);
-    case EPI_GELU_MXFP8: return launch<EPI_GELU_MXFP8>(g, st);
+    case EPI_BF16: return launch_sel<EPI_BF16>(g, kernel, workgroups, st);
+    case EPI_GELU_BF16: return launch_sel<EPI_GELU_BF16>(g, kernel, workgroups, st);
+    case EPI_F32: return launch_sel<EPI_F32>(g, kernel, workgroups, st);
+    case EPI_RES_F32: return launch_sel<EPI_RES_F32>(g, kernel, workgroups, st);
+    case EPI_GELU_MXFP8: return launch_sel<EPI_GELU_MXFP8>(g, kernel, workgroups, st);
     default: return SA_ERR_ARG;
   }
+}
+
+extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                             const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
+                             void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
+                             int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream) {
+  return sa_gemm_mxfp8_ex(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, bias, C, ldc, C_scales, ldcs, M, N, K, epilogue,
+                          residual, ldr, gate, gate_bstride, rows_per_batch, KERNEL_AUTO, 0, stream);
 }
 
 extern "C" int sa_gemm_mxfp8_vt(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,

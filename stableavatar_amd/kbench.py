@@ -5,7 +5,9 @@ against the bf16 kernels, ditfp8 = the whole forward with the mode off and on; a
 launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the whole forward with that mode off, on, and
 on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (LayerNorm .. operands ready) in bf16, with the
 fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused;
-attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16."""
+attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16.
+gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ex's one-tile kernel (the baseline arm) against its persistent kernel on their
+GEMM shapes, and ditfp8qkv has a variant that runs every MXFP8 GEMM of the forward on the persistent kernel."""
 from __future__ import annotations
 
 import json
@@ -112,6 +114,7 @@ def main(which=("gemm", "attn")):
             del x, w, out
     if "gemmfp8" in which:  # the fp8 FFN mode's kernels against the bf16 ones they replace, interleaved rounds
         res.extend(bench_fp8_ffn(M))
+        res.extend(bench_mxgemm_kernels(MXGEMM_FFN_SHAPES))
     if "attnvar" in which:
         import os
         L, H, D = 21504, 12, 128
@@ -286,6 +289,7 @@ def main(which=("gemm", "attn")):
         res.extend(bench_fp8_attn_split())
     if "qkvfp8" in which:  # the fp8 q/k/v mode's operand chains against the bf16 one, interleaved rounds
         res.extend(bench_fp8_qkv())
+        res.extend(bench_mxgemm_kernels(MXGEMM_QKV_SHAPES))
     if "ditfp8qkv" in which:  # whole-forward A/B of enable_fp8_qkv() on top of the other two modes, interleaved
         res.append(bench_dit(fp8_qkv_ab=True))
         print(json.dumps(res[-1]), flush=True)
@@ -500,6 +504,61 @@ def bench_fp8_qkv(L=21504, H=12, B=3):
     return [r, r2]
 
 
+# (name, M, N, K, epilogue): config 2 (M = 3 x 21 504) and the Ulysses N = 8 rank (M = 3 x 2 688) FFN, config-2 q|k, qkv
+MXGEMM_FFN_SHAPES = (("ffn_up", 64512, 8960, 1536, ops.EPI_GELU_TANH_MXFP8), ("ffn_down", 64512, 1536, 8960, ops.EPI_RES_F32),
+                     ("ffn_up_rank8", 8064, 8960, 1536, ops.EPI_GELU_TANH_MXFP8),
+                     ("ffn_down_rank8", 8064, 1536, 8960, ops.EPI_RES_F32))
+MXGEMM_QKV_SHAPES = (("qk", 64512, 3072, 1536, ops.EPI_BF16), ("qkv", 64512, 4608, 1536, ops.EPI_BF16))
+
+
+def bench_mxgemm_kernels(shapes, rounds=5):
+    """sa_gemm_mxfp8_ex's one-tile kernel (kernel=1, the baseline arm) against its persistent kernel (kernel=2, one
+    workgroup per CU) on random MXFP8 operands, same process, interleaved rounds, median of `rounds` per arm, every
+    round kept, spread = (max - min) / median per arm, the graphics clock after each round.  ratio = one-tile ms /
+    persistent ms (> 1: the persistent kernel is faster); `identical`: the two outputs (and scales) byte for byte."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    res = []
+    for name, M, N, K, epi in shapes:
+        x = ops.mxfp8_quant(torch.randn(M, K, device=dev, generator=g).bfloat16())
+        w = ops.mxfp8_quant((torch.randn(N, K, device=dev, generator=g) / K ** 0.5).bfloat16())
+        bias = torch.randn(N, device=dev, generator=g) * 0.1
+        kw = {}
+        if epi == ops.EPI_RES_F32:  # residual in its own buffer, so that repeated launches keep one input
+            kw = dict(residual=torch.randn(M, N, device=dev, generator=g), gate=torch.randn(3, N, device=dev, generator=g),
+                      rows_per_batch=M // 3)
+        if epi == ops.EPI_GELU_TANH_MXFP8:
+            outs = {k: ops.Mx8.empty(M, N, dev) for k in (1, 2)}
+        else:
+            dt = torch.float32 if epi == ops.EPI_RES_F32 else torch.bfloat16
+            outs = {k: torch.empty(M, N, device=dev, dtype=dt) for k in (1, 2)}
+        fns = {"one_tile": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[1], kernel=1, **kw),
+               "persistent": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[2], kernel=2, **kw)}
+        times, clocks = {n: [] for n in fns}, []
+        for _ in range(rounds):
+            for n, fn in fns.items():
+                times[n].append(_time(fn, iters=20, warmup=2))
+            clocks.append(_sclk_mhz())
+        torch.cuda.synchronize()
+        if epi == ops.EPI_GELU_TANH_MXFP8:
+            same = torch.equal(outs[1].q, outs[2].q) and torch.equal(outs[1].s, outs[2].s)
+        else:
+            same = torch.equal(outs[1], outs[2])
+        ms = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
+        r = {"kernel": f"mxgemm_{name}", "M": M, "N": N, "K": K, "epilogue": epi, "tiles": -(-M // 256) * -(-N // 256),
+             "cus": ops._n_cu(x.q.device), "sclk_mhz": clocks, "identical": bool(same)}
+        for n in fns:
+            r[f"{n}_ms"] = round(ms[n], 4)
+            r[f"{n}_tflops"] = round(2.0 * M * N * K / ms[n] / 1e9, 1)
+            r[f"{n}_rounds_ms"] = [round(t, 4) for t in times[n]]
+            r[f"{n}_spread"] = round((max(times[n]) - min(times[n])) / ms[n], 4)
+        r["ratio"] = round(ms["one_tile"] / ms["persistent"], 4)
+        res.append(r)
+        print(json.dumps(r), flush=True)
+        del x, w, outs, kw
+    return res
+
+
 def bench_fp8_ffn(M=3 * 21504, C=1536, FF=8960, rpb=21504):
     """The three kernels of a block's FFN at config 2 (M = 64 512 rows), bf16 (auto kernel) vs MXFP8, same process,
     interleaved rounds, median of 3: LayerNorm + modulate (bf16 out vs MXFP8 out), ffn_up (N 8960, K 1536, GELU;
@@ -652,7 +711,8 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
     and the rel-L2 between their outputs.  fp8_attn_ab: the same for enable_fp8_attention() off, on, and on together
     with enable_fp8_ffn() (three models on the same weights), each output's rel-L2 against off, the graphics clock
     after each round.  fp8_qkv_ab: four variants on the same weights -- off; attention + FFN; those + enable_fp8_qkv()
-    unfused; and fused -- each output's rel-L2 against off, whether fused equals unfused byte for byte."""
+    unfused; fused; and fused with the MXFP8 GEMMs on their persistent kernel -- each output's rel-L2 against off, whether
+    fused equals unfused, and persistent equals fused, byte for byte."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -728,22 +788,37 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
             if k != "attn_ffn":
                 modes[k].enable_fp8_qkv()
                 modes[k]._fp8_qkv_fused = k.endswith("_fused")
+        # the fused variant again with every sa_gemm_mxfp8_ex launch on the persistent kernel: what SA_MXGEMM_KERNEL=2
+        # does to a process (the variable is read once, so one process cannot hold both of its states)
+        import os
+        pers = "attn_ffn_qkv_fused_persistent"
+        modes[pers] = modes["attn_ffn_qkv_fused"]
+        one_tile_or_auto = ops.linear_mxfp8
+
+        def persistent(*a, **kw):
+            return one_tile_or_auto(*a, **dict(kw, kernel=2))
         times, clocks, outs = {k: [] for k in modes}, [], {}
         with torch.no_grad():
             for _ in range(3):
                 for k, mm in modes.items():
                     f = lambda mm=mm: mm.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)  # noqa: E731
-                    times[k].append(_time(f, iters=2, warmup=1))
-                    outs[k] = f().float()
+                    ops.linear_mxfp8 = persistent if k == pers else one_tile_or_auto
+                    try:
+                        times[k].append(_time(f, iters=2, warmup=1))
+                        outs[k] = f().float()
+                    finally:
+                        ops.linear_mxfp8 = one_tile_or_auto
                 clocks.append(_sclk_mhz())
         r = {"kernel": "dit_forward_fp8_qkv_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks,
-             "fused_equals_unfused": bool(torch.equal(outs["attn_ffn_qkv_fused"], outs["attn_ffn_qkv_unfused"]))}
+             "SA_MXGEMM_KERNEL": os.environ.get("SA_MXGEMM_KERNEL"),
+             "fused_equals_unfused": bool(torch.equal(outs["attn_ffn_qkv_fused"], outs["attn_ffn_qkv_unfused"])),
+             "persistent_equals_fused": bool(torch.equal(outs[pers], outs["attn_ffn_qkv_fused"]))}
         for k in modes:
             r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
             if k != "off":
                 r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
                 r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
-        for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused"):
+        for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused", pers):
             r[f"ratio_{k}_vs_attn_ffn"] = round(r["attn_ffn_ms"] / r[f"{k}_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
