@@ -176,7 +176,7 @@ class UlyssesExchange:
         # + slack rows: the O-projection's last tile reads up to its tile height past the last panel
         # (sa_gemm_bf16_panels; the buffer range check does not cover the panel offset).  The slack comes from
         # the library (sa_gemm_panel_slack_rows = the tallest GEMM tile), so a taller tile cannot outgrow it.
-        # On the per-row-stream path (transformer._sp_layer_rows) row b's O-projection tail tile also reads
+        # On the per-row-stream path (transformer._sp_block_streams) row b's O-projection tail tile also reads
         # into row b+1's panel region while another stream may be writing it: benign, those rows' products are
         # discarded (never stored), only their bytes are fetched.
         self.obuf = torch.empty(2 * G * B * Lc + _panel_slack_rows(device), hgd, device=device, dtype=dtype)

@@ -18,6 +18,7 @@ import glob
 import json
 import math
 import os
+from contextlib import contextmanager
 from types import SimpleNamespace
 
 import torch
@@ -205,6 +206,31 @@ class _Seg:
         return lay
 
 
+SP_BATCHED, SP_ROWS, SP_ROWS_X, SP_STREAMS = "0", "2", "3", "4"  # the exchange schedules, by their SA_SP_OVERLAP value
+
+
+def sp_schedule(overlap: str, B: int, wg_row: int, n_cu: int, gpu: bool) -> str:
+    """The sequence-parallel exchange schedule of the DiT blocks for SA_SP_OVERLAP = `overlap`: 0 one synchronous
+    batched exchange per direction; 2 per-row exchanges and per-row attention; 3 per-row Q/K/V exchanges, batched
+    attention; 4 every CFG row through the whole block on its own HIP stream (more than one row, on a GPU); 1 = auto:
+    4, else 2 when per-row attention launches add no waves over the CUs -- a row's launch has wg_row = ceil(Lq / 256)
+    x hg workgroups and B serial launches must not need more rounds than the batched one -- else 3 (N = 8: 63
+    workgroups per row would leave most CUs idle, but the Q/K/V exchange of row b can still travel under the QKV GEMMs
+    of rows b+1..; per-row GEMMs there take as many rounds over the CUs as the batched one).  With a single row 3 and
+    4 are the batched schedule."""
+    if overlap == "1":
+        if B > 1 and gpu:
+            # one stream per CFG row through the whole block: its compute alone matches the best of the
+            # other schedules at every degree (per-rank forward with the transfers stubbed out, N = 2 / 4 / 8:
+            # 197.2 / 103.3 / 59.3 ms vs 198.5 / 103.8 / 59.0 ms, profiles/r04/sp_rank_compute_r4s.jsonl)
+            # and every transfer travels under the other rows' work
+            return SP_STREAMS
+        return SP_ROWS if B * -(-wg_row // n_cu) <= -(-(B * wg_row) // n_cu) else SP_ROWS_X
+    if overlap == SP_ROWS or (overlap == SP_ROWS_X and B > 1) or (overlap == SP_STREAMS and B > 1 and gpu):
+        return overlap
+    return SP_BATCHED
+
+
 class WanTransformer3DFantasyModel(nn.Module):
     """Audio-driven Wan-2.1 DiT (1B:741-1184) on HIP kernels."""
 
@@ -246,6 +272,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         # with _fp8_qkv and _fp8_attn both on, the single-GPU sites write the attention operands where their values are
         # made (_self_attention_rows); False: the mode's GEMM, then _self_attn -- the same output bytes (for the A/B)
         self._fp8_qkv_fused = True
+        self._rstreams = None  # _row_streams(): the HIP streams of the per-CFG-row sequence-parallel schedule
         self._packed = None
         self._ws = {}
         self._ctx_cache = None
@@ -384,22 +411,24 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._packed = None
             self._ws = {}
 
-    def _self_attn(self, ws, q, k, v, out, segs, nseg, max_q_len, heads, kernel=0, o_rows=None, split_tiles=0):
-        """One self-attention launch of a DiT block: ops.attention, or with enable_fp8_attention() the K means, the
-        operand pack and the MXFP8 flash kernel (ops.attention_mxfp8); split_tiles (ops.attn_tail_split, given by the
-        sequence-parallel sites alone; in fp8 mode by the batched one alone, see _sp_layer_rows) goes to either.  The
-        operand buffers and the split's scratch live
-        in the workspace, one set per segment table (the per-row streams of the sequence-parallel schedule run
-        concurrently, each on its own table), allocated on first use."""
+    def _self_attn(self, f, q, k, v, out, segs, kernel=0, split_tiles=0):
+        """One self-attention launch of a DiT block over the segment table `segs` (f: the forward's state, whose Lq,
+        hg and omap are the launch's query rows per segment, heads and output row map): ops.attention, or with
+        enable_fp8_attention() the K means, the operand pack and the MXFP8 flash kernel (ops.attention_mxfp8);
+        split_tiles (ops.attn_tail_split, given by the sequence-parallel sites alone; in fp8 mode by the batched one
+        alone, see _sp_block_streams) goes to either.  The operand buffers and the split's scratch live in the
+        workspace, one set per segment table (the per-row streams run concurrently, each on its own table), allocated
+        on first use."""
+        nseg = segs.shape[0]
         if not self._fp8_attn:
-            return ops.attention(q, k, v, out, segs, nseg, max_q_len, heads, kernel=kernel, o_rows=o_rows,
+            return ops.attention(q, k, v, out, segs, nseg, f.Lq, f.hg, kernel=kernel, o_rows=f.omap,
                                  split_tiles=split_tiles)
         vcol0, Rv, max_kv = self._segs.vt_layout(segs)
-        key = (id(segs), q.shape[0], k.shape[0], heads)
-        buf = ws.attn8.get(key)
+        key = (id(segs), q.shape[0], k.shape[0], f.hg)
+        buf = f.ws.attn8.get(key)
         if buf is None:
-            buf = ws.attn8[key] = ops.AttnMx8(q.shape[0], k.shape[0], heads, Rv, nseg, q.device)
-        return ops.attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv, buf, o_rows=o_rows,
+            buf = f.ws.attn8[key] = ops.AttnMx8(q.shape[0], k.shape[0], f.hg, Rv, nseg, q.device)
+        return ops.attention_mxfp8(q, k, v, out, segs, nseg, f.Lq, f.hg, vcol0, max_kv, buf, o_rows=f.omap,
                                    split_tiles=split_tiles)
 
     def enable_multi_gpus_inference(self, group=None, loopback=None):
@@ -461,7 +490,7 @@ class WanTransformer3DFantasyModel(nn.Module):
                                    for n in ("k", "v")], 0).float().contiguous()
         for i in range(self.num_layers):
             p = f"blocks.{i}."
-            L = SimpleNamespace()
+            L = SimpleNamespace(i=i)  # i: the block's index (its rows of the per-forward context and vocal K|V)
             L.w_qkv = cat_bf(p + "self_attn.q.weight", p + "self_attn.k.weight", p + "self_attn.v.weight")
             L.b_qkv = cat_f(p + "self_attn.q.bias", p + "self_attn.k.bias", p + "self_attn.v.bias")
             if self._fp8_qkv:  # quantised along K on the GPU (= mxfp8.quantize), the bf16 copy dropped
@@ -618,7 +647,7 @@ class WanTransformer3DFantasyModel(nn.Module):
 
     # ------------------------------------------------------------------ vocal projector
 
-    def _vocal(self, pk, vocal_embeddings, n_frames, lat_bf16, Lq, e0_row, e_row, dev, frames=None):
+    def _vocal(self, pk, vocal_embeddings, n_frames, lat_bf16, Lq, e0_row, e_row, frames=None):
         """FantasyTalkingVocalCondition{1B,14B}Model.forward (vocal_projector_fantasy_1B.py:433-450,
         _14B.py:431-449) for one audio row; lat_bf16 = patch-embedded tokens of that row [Lq, dim].
         Returns [F*n, vd] bf16 (vd = 1536 for 1.3B, the DiT width for 14B).
@@ -626,7 +655,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         [nf*n, vd]).  Every op of the projector is per row except the attention, whose queries of frame f attend only
         to frame f's tokens (:259-270), so these rows equal those of the whole projector bit for bit: a
         sequence-parallel rank computes the frames its token chunk covers."""
-        V, vd = pk.vocal, self.vd
+        V, vd, dev = pk.vocal, self.vd, lat_bf16.device
         hdv = vd // 8  # 8 heads: D = 192 (1.3B) or 640 (14B)
         feat = vocal_embeddings.to(device=dev, dtype=torch.bfloat16).contiguous()
         Na = feat.shape[0]
@@ -672,29 +701,186 @@ class WanTransformer3DFantasyModel(nn.Module):
         ops.layernorm_mod(x, hb, 1e-6, shift=ef[0, 0, 0:1], scale=ef[0, 0, 1:2], rows_per_batch=Mv)
         return ops.linear(hb, V.w_fp, V.b_fp, ops.EPI_BF16), Fn, nper
 
-    # ------------------------------------------------------------------ sequence parallel, one stream per CFG row
+    # ------------------------------------------------------------------ the steps of a DiT block
+    # Each takes the forward's state f (forward_window), the layer's packed weights L, the layer's modulation em
+    # [B, 6, dim] where it reads one, and a row selector b: None = all B CFG rows in one launch, b = CFG row b alone.
+    # The selector resolves to R = f.all or f.row[b]: the rows' range, workspace views and tables (_plan_blocks).
 
     def _row_streams(self, B, dev):
         """B HIP streams (one per CFG row) for the SP_OVERLAP=4 layer schedule, kept per device"""
-        st = getattr(self, "_rstreams", None)
+        st = self._rstreams
         if st is None or len(st) < B or st[0].device != dev:
             st = self._rstreams = [torch.cuda.Stream(dev) for _ in range(B)]
         return st[:B]
 
-    def _row_cross_segs(self, B, Lc, ctx, voc_list, dev):
-        """per-row cross-attention segment tables (query rows relative to the row's chunk, key rows absolute in the
-        shared text / image / vocal K|V buffers) for the three-launch path"""
-        out = []
-        for b in range(B):
-            txt = self._segs.get(("rtxt", b, Lc, ctx.text_len), [[0, Lc, b * ctx.text_len, ctx.text_len]], dev)
-            img = self._segs.get(("rimg", b, Lc, ctx.img_len), [[0, Lc, b * ctx.img_len, ctx.img_len]], dev)
-            vl = [[q0 - b * Lc, ql, k0, kl] for q0, ql, k0, kl in voc_list if b * Lc <= q0 < (b + 1) * Lc]
-            voc = self._segs.get(("rvoc", b, Lc, tuple(map(tuple, vl))), vl, dev)
-            out.append((txt, img, voc, len(vl), max(s_[1] for s_ in vl)))
-        return out
+    @staticmethod
+    def _sel(f, b, em=None):
+        """row selector -> (the rows' views and tables R, their modulation [rows, 6, dim])"""
+        if b is None:
+            return f.all, em
+        return f.row[b], None if em is None else em[b:b + 1]
 
-    def _sp_layer_rows(self, pk, L, li, x, ws, em, ex, pack_kw, rank, Lc, Lq, hg, hgd, grid, segs_rows, row_segs,
-                       ctx, kvv, nper, Gf, n_fr, use_cross3, rstreams, sa=True):
+    def _norm1(self, f, R, e):
+        """norm1 + modulate (1B:675) of the rows R of the residual stream: bf16 ws.mod, or
+        with enable_fp8_qkv() MXFP8 ws.modq (bf16 output followed by the quantiser, in one kernel)"""
+        ln, out = (ops.layernorm_mod_mxfp8, R.modq) if self._fp8_qkv else (ops.layernorm_mod, R.mod)
+        return ln(R.x, out, self.eps, shift=e[:, 0], scale=e[:, 1], rows_per_batch=f.Lc)
+
+    def _qkv(self, f, L, R, e, normed=False):
+        """The q|k|v Linears of a block's self-attention (1B:383-390) for the rows R of the residual stream: norm1 +
+        modulate (unless `normed`: _norm1 already ran), then the fused QKV GEMM into their ws.qkv rows as bf16.  With
+        enable_fp8_qkv() the LayerNorm writes MXFP8 and the GEMM runs on the block-scaled fp8 MFMA; off, exactly the
+        bf16 calls."""
+        if not normed:
+            self._norm1(f, R, e)
+        lin, mod = (ops.linear_mxfp8, R.modq) if self._fp8_qkv else (ops.linear, R.mod)
+        return lin(mod, L.w_qkv, L.b_qkv, ops.EPI_BF16, out=R.qkv)
+
+    def _sp_send_qkv(self, f, L, em, b, normed=False):
+        """Self-attention inputs (1B:675-676) of the selected rows and their Q/K/V exchange (wan_xfuser.py:102-107): QKV
+        GEMM, RMSNorm + RoPE packed into the send slabs / attention inputs, the transfers issued; returns the Pending"""
+        R, e = self._sel(f, b, em)
+        self._qkv(f, L, R, e, normed=normed)
+        ops.qkv_pack(R.qkv, L.nq, L.nk, self.dim, self.eps, b_offset=R.rows.start, **f.pack_kw, **f.rope_kw)
+        return f.ex.heads(R.rows)
+
+    def _sp_attend(self, f, b, pend, kernel, split_tiles):
+        """Ulysses: once the Q/K/V transfers `pend` have arrived, full-sequence attention of this rank's (query part,
+        head group) for the selected rows, outputs written to the owners' send slabs / this rank's own O-projection
+        panel, then heads -> tokens issued.  Returns the Pending."""
+        for p_ in pend:
+            p_.wait()
+        R, ex = self._sel(f, b)[0], f.ex
+        with self._span(rows=len(R.rows), batch=f.B):
+            self._self_attn(f, ex.q, f.k, f.v, ex.obuf, R.self_attn, kernel=kernel, split_tiles=split_tiles)
+        return ex.tokens(R.rows)
+
+    def _sp_o_proj(self, f, L, em, b, back):
+        """the head outputs `back` of the selected rows received, their O-projection over the column panels +
+        gated residual (1B:677-679)"""
+        R, e = self._sel(f, b, em)
+        back.wait()
+        a0, pnl = f.ex.panels(R.rows)
+        ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=R.x, residual=R.x, gate=e[:, 2], rows_per_batch=f.Lc,
+                   a_panels=pnl)
+
+    def _self_attention_rows(self, f, L, em, b=None, normed=False):
+        """The self-attention half of a block (1B:675-679) on the single-GPU layout, for all CFG rows or row 0 (the
+        shared first block): LN + modulate (unless `normed`), q|k (+ v as V^T for kernel 3, or q|k|v rows), RMSNorm +
+        RoPE, attention, O-projection + gated residual into x.  With enable_fp8_qkv() and enable_fp8_attention() (and
+        _fp8_qkv_fused) the fused chain: q|k GEMM, the V GEMM writing the V^T operand, RMSNorm + RoPE writing the Q
+        operand, K means, K pack, the MXFP8 flash kernel."""
+        dim, H_, ws, Lc, Lp = self.dim, self.num_heads, f.ws, f.Lc, f.Lp
+        R, e = self._sel(f, b, em)
+        nb, segs, xr, mod, qkv, att = len(R.rows), R.self_attn, R.x, R.mod, R.qkv, R.att
+        if not normed:
+            self._norm1(f, R, e)
+        if self._fp8_qkv and self._fp8_attn and self._fp8_qkv_fused:
+            assert Lc == Lp and not f.use_vt
+            vcol0, Rv, max_kv = self._segs.vt_layout(segs)
+            key = (id(segs), nb * Lc, nb * Lc, H_)
+            buf = ws.attn8.get(key)
+            if buf is None:
+                buf = ws.attn8[key] = ops.AttnMx8(nb * Lc, nb * Lc, H_, Rv, nb, f.dev)
+            modq = R.modq
+            ops.linear_mxfp8(modq, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
+            ops.linear_mxfp8_vt(modq, L.w_v, L.b_v, Lp, nb, buf)
+            ops.qk_rmsnorm_rope_mxfp8(qkv, 0, dim, L.nq, L.nk, dim, self.eps, buf, **f.rope_kw)
+            with self._span(rows=nb, batch=f.B):
+                km = ops.attn_kmean(qkv[:, dim:2 * dim], segs, nb, H_, buf.kmean, buf.kmean_work)
+                ops.attn_pack_k_mxfp8(qkv[:, dim:2 * dim], segs, nb, max_kv, H_, buf, km)
+                ops.attn_fwd_mxfp8(buf, att, segs, vcol0, nb, Lp, H_)
+        elif f.use_vt:
+            # q|k into the QKV rows, v straight into V^T (keys in P's order per 32) for attention kernel 3
+            ops.linear(mod, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
+            ops.linear(mod, L.w_v, L.b_v, ops.EPI_BF16_TP32, out=ws.vt)
+            ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **f.rope_kw)
+            with self._span(rows=nb, batch=f.B):
+                ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_, kernel=ops.ATTN_VT_P32)
+        else:
+            self._qkv(f, L, R, e, normed=True)
+            ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **f.rope_kw)
+            with self._span(rows=nb, batch=f.B):
+                self._self_attn(f, qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs,
+                                kernel=self.attn_kernel)
+        ops.linear(att, L.w_o, L.b_o, ops.EPI_RES_F32, out=xr, residual=xr, gate=e[:, 2], rows_per_batch=Lc)
+
+    def _cross_attention(self, f, L, b):
+        """cross-attention of the selected rows: text + image + per-frame vocal (1B:534-605, 684), its output
+        projection added to the residual stream.  A row alone reads its own rows of the text / image / vocal K|V
+        (cross3), or the shared K|V through its own segment tables (the three launches)."""
+        dim, H_, eps, ctx = self.dim, self.num_heads, self.eps, f.ctx
+        R = self._sel(f, b)[0]
+        nb, xr, mod, att = len(R.rows), R.x, R.mod, R.att
+        ops.layernorm_mod(xr, mod, eps, weight=L.n3w, bias=L.n3b)
+        qc = R.qkv[:, :dim]
+        ops.linear(mod, L.w_cq, L.b_cq, ops.EPI_BF16, out=qc)
+        ops.qk_rmsnorm_rope(qc, 0, -1, L.cnq, None, dim, eps)
+        (kvt, kvi), kvv = ctx.kv[L.i], f.kvv[L.i]
+        if f.use_cross3:  # text + image + vocal in one launch, bf16 sum as 1B:602
+            if b is not None:
+                tl, ni, nv = ctx.text_len, ctx.img_len, f.n_fr * f.nper
+                kvt, kvi, kvv = kvt[b * tl:(b + 1) * tl], kvi[b * ni:(b + 1) * ni], kvv[b * nv:(b + 1) * nv]
+            ops.attention_cross3(qc, kvt[:, :dim], kvt[:, dim:], ctx.text_len, kvi[:, :dim], kvi[:, dim:],
+                                 ctx.img_len, kvv[:, :dim], kvv[:, dim:], f.nper, f.G, f.n_fr, att, nb, f.Lc, H_,
+                                 tok_offset=f.rank * f.Lc)
+        else:
+            ops.attention(qc, kvt[:, :dim], kvt[:, dim:], att, R.txt, nb, f.Lc, H_)
+            if kvi is not None:
+                ops.attention(qc, kvi[:, :dim], kvi[:, dim:], att, R.img, nb, f.Lc, H_, accumulate=True)
+            ops.attention(qc, kvv[:, :dim], kvv[:, dim:], att, R.voc, R.voc_n, R.voc_q, H_, accumulate=True)
+        ops.linear(att, L.w_co, L.b_co, ops.EPI_RES_F32, out=xr, residual=xr)
+
+    def _ffn(self, f, L, em, b):
+        """The FFN third of a block (1B:687-691) on the selected rows of the residual stream: norm2 +
+        modulate, ffn.0 + GELU, ffn.2 + gated residual into x.  With enable_fp8_ffn() the LayerNorm writes MXFP8,
+        ffn.0's epilogue hands ffn.2 its operand as MXFP8 and both GEMMs run on the block-scaled fp8 MFMA."""
+        R, e = self._sel(f, b, em)
+        x, ffn, Lc = R.x, R.ffn, f.Lc
+        if self._fp8_ffn:
+            ln, lin, mod, gelu = ops.layernorm_mod_mxfp8, ops.linear_mxfp8, R.modq, ops.EPI_GELU_TANH_MXFP8
+        else:
+            ln, lin, mod, gelu = ops.layernorm_mod, ops.linear, R.mod, ops.EPI_GELU_TANH_BF16
+        ln(x, mod, self.eps, shift=e[:, 3], scale=e[:, 4], rows_per_batch=Lc)
+        lin(mod, L.w_f0, L.b_f0, gelu, out=ffn)
+        lin(ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=e[:, 5], rows_per_batch=Lc)
+
+    # ------------------------------------------------------------------ the schedules of a DiT block (1B:650-695)
+
+    def _shared_first_block(self, f, L, em):
+        """The first block's self-attention half (1B:675-679) for CFG row 0 alone -- under sequence parallelism through
+        the Ulysses exchange (its Q/K/V and head outputs only, unsplit), on the current stream -- the residual stream
+        then copied to rows 1..B-1: the CFG rows enter the block identical (shared_rows), every rank takes this path"""
+        if f.ex is None:
+            self._self_attention_rows(f, L, em, 0)
+        else:
+            back = self._sp_attend(f, 0, [self._sp_send_qkv(f, L, em, 0)], self.attn_kernel, 0)
+            self._sp_o_proj(f, L, em, 0, back)
+        x, Lc = f.ws.x, f.Lc
+        for b in range(1, f.B):
+            x[b * Lc:(b + 1) * Lc].copy_(x[:Lc])
+        if f.schedule == SP_STREAMS:
+            for st in f.streams:
+                st.wait_stream(f.main)
+
+    def _sp_self_attention(self, f, L, em):
+        """The self-attention half of a block (norm1 done) under the one-stream Ulysses schedules."""
+        # one exchange per direction for all rows, or per-row Q/K/V exchanges issued as each row's QKV GEMM + pack
+        # lands (they travel under the later rows' GEMMs)
+        sent = [None] if f.schedule == SP_BATCHED else range(f.B)
+        pend = [self._sp_send_qkv(f, L, em, b, normed=True) for b in sent]
+        if f.schedule == SP_ROWS:
+            # Ulysses pipelined over the CFG rows: row b's attention waits only on its own exchange, and row b's output
+            # exchange travels under the next rows' attention and the earlier rows' O-projections.  No launch is split
+            back = [self._sp_attend(f, b, [pend[b]], self.attn_kernel, 0) for b in sent]
+            for b in sent:
+                self._sp_o_proj(f, L, em, b, back[b])
+            return
+        # one batched attention once all have arrived, its tiles past the last full round over the CUs as key halves
+        split = ops.attn_tail_split(0, f.B * f.hg * -(-f.Lq // 256), f.dev) if self.attn_kernel == 0 else 0
+        self._sp_o_proj(f, L, em, None, self._sp_attend(f, None, pend, self.attn_kernel, split))
+
+    def _sp_block_streams(self, f, L, em, sa):
         """One DiT block (1B:650-695) with Ulysses sequence parallelism, each CFG row on its own stream
         (SA_SP_OVERLAP=4): row b's Q/K/V exchange (wan_xfuser.py:102-107) travels while the other rows compute
         (their QKV GEMMs, attention, O-projection, cross-attention and FFN), and its head-output exchange travels
@@ -702,178 +888,240 @@ class WanTransformer3DFantasyModel(nn.Module):
         (QKV+pack+send for every row, then attention+send back for every row, then the rest of the block), so the
         transport sees the same order of transfers on every rank.  Per-row kernels are the batched ones applied to
         row slices: the output is bit-identical to the batched schedule.  sa=False: the self-attention half already
-        ran (_sp_self_attention_row0), the block starts at its cross-attention."""
-        dim, H_, eps = self.dim, self.num_heads, self.eps
-        B = len(rstreams)
-        rope_kw = dict(rope=pk.rope, rows_per_batch=Lc, tok_offset=rank * Lc, grid=grid, head_dim=self.d,
-                       n_frame_pairs=self.d // 2 - 2 * (self.d // 6), n_height_pairs=self.d // 6)
-        tl, ni = ctx.text_len, ctx.img_len
-        kvt, kvi = ctx.kv[li]
-        nv = n_fr * nper
-        pend, back = [], []
+        ran (_shared_first_block), the block starts at its cross-attention."""
         # the rows' attention launches run concurrently: the tiles past their last full round over the CUs (in the
         # last row's launch) run as key halves (ops.attn_tail_split), all rows on the 8-wave kernel then.  Not in
         # the fp8 attention mode: there the three concurrent launches measured 3 % slower with the last row's tail
         # split than without (profiles/r10/fp8_attn_split.jsonl), so its key split serves the batched launch alone
-        n_row = hg * -(-Lq // 256)
-        splits = [ops.attn_tail_split(b * n_row, n_row, x.device) if self.attn_kernel == 0 and not self._fp8_attn
-                  else 0 for b in range(B)]
+        n_row = f.hg * -(-f.Lq // 256)
+        splits = [ops.attn_tail_split(b * n_row, n_row, f.dev) if self.attn_kernel == 0 and not self._fp8_attn
+                  else 0 for b in range(f.B)]
         akern = 1 if any(splits) else self.attn_kernel
-        for b, st in enumerate(rstreams if sa else []):  # self-attention inputs (1B:675-676) and the Q/K/V exchange
-            rs = slice(b * Lc, (b + 1) * Lc)
+        pend, back = [], []
+        for b, st in enumerate(f.streams if sa else []):  # self-attention inputs (1B:675-676) and the Q/K/V exchange
             with torch.cuda.stream(st):
-                self._qkv(L, x[rs], ws, rs, em[b:b + 1, 0], em[b:b + 1, 1], Lc)
-                ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, eps, b_offset=b, **pack_kw, **rope_kw)
-                pend.append(ex.heads([b]))
-        for b, st in enumerate(rstreams if sa else []):  # attention over every key, head outputs back to the owners
+                pend.append(self._sp_send_qkv(f, L, em, b))
+        for b, st in enumerate(f.streams if sa else []):  # attention over every key, head outputs back to the owners
             with torch.cuda.stream(st):
-                pend[b].wait()
-                ev0 = self._record_event()
-                self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq, hg,
-                                kernel=akern, o_rows=ex.omap, split_tiles=splits[b])
-                self._record_span(ev0, rows=1, batch=B)
-                back.append(ex.tokens([b]))
-        for b, st in enumerate(rstreams):  # O-projection + gated residual, cross-attention, FFN (1B:677-691)
-            rs = slice(b * Lc, (b + 1) * Lc)
-            xr, mod, att = x[rs], ws.mod[rs], ws.att[rs]
+                back.append(self._sp_attend(f, b, [pend[b]], akern, splits[b]))
+        for b, st in enumerate(f.streams):  # O-projection + gated residual, cross-attention, FFN (1B:677-691)
             with torch.cuda.stream(st):
                 if sa:
-                    back[b].wait()
-                    a0, pnl = ex.panels(range(b, b + 1))
-                    ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=xr, residual=xr, gate=em[b:b + 1, 2],
-                               rows_per_batch=Lc, a_panels=pnl)
-                ops.layernorm_mod(xr, mod, eps, weight=L.n3w, bias=L.n3b)
-                qc = ws.qkv[rs, :dim]
-                ops.linear(mod, L.w_cq, L.b_cq, ops.EPI_BF16, out=qc)
-                ops.qk_rmsnorm_rope(qc, 0, -1, L.cnq, None, dim, eps)
-                kv_b = kvv[b * nv:(b + 1) * nv]
-                if use_cross3:
-                    kt, ki = kvt[b * tl:(b + 1) * tl], kvi[b * ni:(b + 1) * ni]
-                    ops.attention_cross3(qc, kt[:, :dim], kt[:, dim:], tl, ki[:, :dim], ki[:, dim:], ni, kv_b[:, :dim],
-                                         kv_b[:, dim:], nper, Gf, n_fr, att, 1, Lc, H_, tok_offset=rank * Lc)
+                    self._sp_o_proj(f, L, em, b, back[b])
+                self._cross_attention(f, L, b)
+                self._ffn(f, L, em, b)
+
+    def _blocks(self, f, emod):
+        """the layer loop (1B:650-695 for every block) in the forward's schedule"""
+        streams = f.schedule == SP_STREAMS
+        if streams:  # every CFG row through the whole layer on its own HIP stream; rows are independent
+            for st in f.streams:
+                st.wait_stream(f.main)
+        for L in f.pk.layers:
+            em = emod[L.i]  # [B, 6, dim]
+            # the CFG rows enter the first block identical (shared_rows): its self-attention half for
+            # row 0 only, then the residual stream copied to the other rows
+            sa = not (L.i == 0 and f.dedup)
+            if not sa:
+                self._shared_first_block(f, L, em)
+            if streams:
+                self._sp_block_streams(f, L, em, sa)
+                continue
+            if sa:  # self-attention (1B:675-679)
+                self._norm1(f, f.all, em)
+                if f.ex is None:
+                    self._self_attention_rows(f, L, em, normed=True)
                 else:
-                    s_txt, s_img, s_voc, n_voc, q_voc = row_segs[b]
-                    ops.attention(qc, kvt[:, :dim], kvt[:, dim:], att, s_txt, 1, Lc, H_)
-                    if kvi is not None:
-                        ops.attention(qc, kvi[:, :dim], kvi[:, dim:], att, s_img, 1, Lc, H_, accumulate=True)
-                    ops.attention(qc, kvv[:, :dim], kvv[:, dim:], att, s_voc, n_voc, q_voc, H_, accumulate=True)
-                ops.linear(att, L.w_co, L.b_co, ops.EPI_RES_F32, out=xr, residual=xr)
-                self._ffn(L, xr, ws, rs, em[b:b + 1, 3], em[b:b + 1, 4], em[b:b + 1, 5], Lc)
-
-    def _norm1(self, x, ws, rows, shift, scale, Lc):
-        """norm1 + modulate (1B:675) of the rows x of the residual stream into workspace rows `rows`: bf16 ws.mod, or
-        with enable_fp8_qkv() MXFP8 ws.modq (bf16 output followed by the quantiser, in one kernel)"""
-        if self._fp8_qkv:
-            return ops.layernorm_mod_mxfp8(x, ws.modq[rows], self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
-        return ops.layernorm_mod(x, ws.mod[rows], self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
-
-    def _qkv(self, L, x, ws, rows, shift, scale, Lc, normed=False, out=None):
-        """The q|k|v Linears of a block's self-attention (1B:383-390) for the rows x of the residual stream (workspace
-        rows `rows`): norm1 + modulate (unless `normed`: _norm1 already ran), then the fused QKV GEMM into `out`
-        (default ws.qkv[rows]) as bf16.  With enable_fp8_qkv() the LayerNorm writes MXFP8 and the GEMM runs on the
-        block-scaled fp8 MFMA; off, exactly the bf16 calls."""
-        if not normed:
-            self._norm1(x, ws, rows, shift, scale, Lc)
-        out = ws.qkv[rows] if out is None else out
-        if self._fp8_qkv:
-            return ops.linear_mxfp8(ws.modq[rows], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=out)
-        return ops.linear(ws.mod[rows], L.w_qkv, L.b_qkv, ops.EPI_BF16, out=out)
-
-    def _ffn(self, L, x, ws, rows, shift, scale, gate, Lc):
-        """The FFN third of a block (1B:687-691) on the rows x of the residual stream (workspace rows `rows`): norm2 +
-        modulate, ffn.0 + GELU, ffn.2 + gated residual into x.  With enable_fp8_ffn() the LayerNorm writes MXFP8,
-        ffn.0's epilogue hands ffn.2 its operand as MXFP8 and both GEMMs run on the block-scaled fp8 MFMA."""
-        if self._fp8_ffn:
-            mod, ffn = ws.modq[rows], ws.ffn[rows]
-            ops.layernorm_mod_mxfp8(x, mod, self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
-            ops.linear_mxfp8(mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_MXFP8, out=ffn)
-            ops.linear_mxfp8(ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=gate, rows_per_batch=Lc)
-            return
-        mod, ffn = ws.mod[rows], ws.ffn[rows]
-        ops.layernorm_mod(x, mod, self.eps, shift=shift, scale=scale, rows_per_batch=Lc)
-        ops.linear(mod, L.w_f0, L.b_f0, ops.EPI_GELU_TANH_BF16, out=ffn)
-        ops.linear(ffn, L.w_f2, L.b_f2, ops.EPI_RES_F32, out=x, residual=x, gate=gate, rows_per_batch=Lc)
+                    self._sp_self_attention(f, L, em)
+            self._cross_attention(f, L, None)
+            self._ffn(f, L, em, None)  # FFN (1B:687-691)
+        if streams:
+            for st in f.streams:
+                f.main.wait_stream(st)
 
     # ------------------------------------------------------------------ timing hooks (bench.py)
 
-    def _sp_self_attention_row0(self, L, x, ws, em, ex, pack_kw, rope_kw, Lc, Lq, hg, hgd, seg0, B):
-        """The first block's self-attention half (1B:675-679) for CFG row 0 through the Ulysses exchange (its Q/K/V
-        and head outputs only), on the current stream, the residual stream then copied to rows 1..B-1: the CFG rows
-        enter the block identical (forward_window shared_rows), and every rank takes this path together"""
-        dim, eps = self.dim, self.eps
-        rs = slice(0, Lc)
-        self._qkv(L, x[rs], ws, rs, em[0:1, 0], em[0:1, 1], Lc)
-        ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, eps, b_offset=0, **pack_kw, **rope_kw)
-        ex.heads([0]).wait()
-        ev0 = self._record_event()
-        self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, seg0, 1, Lq, hg, kernel=self.attn_kernel,
-                        o_rows=ex.omap)
-        self._record_span(ev0, rows=1, batch=B)
-        ex.tokens([0]).wait()
-        a0, pnl = ex.panels(range(0, 1))
-        ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=x[rs], residual=x[rs], gate=em[0:1, 2], rows_per_batch=Lc,
-                   a_panels=pnl)
-        for b in range(1, B):
-            x[b * Lc:(b + 1) * Lc].copy_(x[rs])
-
-    def _self_attention_rows(self, pk, L, x, ws, em, nb, Lc, Lp, use_vt, rope_kw, dev, batch, normed=False):
-        """The self-attention half of a block (1B:675-679) on the first nb CFG rows of the single-GPU layout: LN +
-        modulate (unless `normed`), q|k (+ v as V^T for kernel 3, or q|k|v rows), RMSNorm + RoPE, attention,
-        O-projection + gated residual into x.  With enable_fp8_qkv() and enable_fp8_attention() (and _fp8_qkv_fused)
-        the fused chain: q|k GEMM, the V GEMM writing the V^T operand, RMSNorm + RoPE writing the Q operand, K means,
-        K pack, the MXFP8 flash kernel."""
-        dim, H_ = self.dim, self.num_heads
-        r = slice(0, nb * Lc)
-        xr, mod, qkv, att = x[r], ws.mod[r], ws.qkv[r], ws.att[r]
-        if not normed:
-            self._norm1(xr, ws, r, em[:nb, 0], em[:nb, 1], Lc)
-        segs = self._segs.get(("self", nb, Lp), [[b * Lp, Lp, b * Lp, Lp] for b in range(nb)], dev)
-        if self._fp8_qkv and self._fp8_attn and self._fp8_qkv_fused:
-            assert Lc == Lp and not use_vt
-            vcol0, Rv, max_kv = self._segs.vt_layout(segs)
-            key = (id(segs), nb * Lc, nb * Lc, H_)
-            buf = ws.attn8.get(key)
-            if buf is None:
-                buf = ws.attn8[key] = ops.AttnMx8(nb * Lc, nb * Lc, H_, Rv, nb, dev)
-            modq = ws.modq[r]
-            ops.linear_mxfp8(modq, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
-            ops.linear_mxfp8_vt(modq, L.w_v, L.b_v, Lp, nb, buf)
-            ops.qk_rmsnorm_rope_mxfp8(qkv, 0, dim, L.nq, L.nk, dim, self.eps, buf, **rope_kw)
-            ev0 = self._record_event()
-            km = ops.attn_kmean(qkv[:, dim:2 * dim], segs, nb, H_, buf.kmean, buf.kmean_work)
-            ops.attn_pack_k_mxfp8(qkv[:, dim:2 * dim], segs, nb, max_kv, H_, buf, km)
-            ops.attn_fwd_mxfp8(buf, att, segs, vcol0, nb, Lp, H_)
-        elif use_vt:
-            # q|k into the QKV rows, v straight into V^T (keys in P's order per 32) for attention kernel 3
-            ops.linear(mod, L.w_qk, L.b_qk, ops.EPI_BF16, out=qkv[:, :2 * dim])
-            ops.linear(mod, L.w_v, L.b_v, ops.EPI_BF16_TP32, out=ws.vt)
-            ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **rope_kw)
-            ev0 = self._record_event()
-            ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_, kernel=ops.ATTN_VT_P32)
-        else:
-            self._qkv(L, xr, ws, r, None, None, Lc, normed=True)
-            ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **rope_kw)
-            ev0 = self._record_event()
-            self._self_attn(ws, qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs, nb, Lp, H_,
-                            kernel=self.attn_kernel)
-        self._record_span(ev0, rows=nb, batch=batch)
-        ops.linear(att, L.w_o, L.b_o, ops.EPI_RES_F32, out=xr, residual=xr, gate=em[:nb, 2], rows_per_batch=Lc)
-
-    def _record_event(self):
-        """HIP event on the current stream (the one the attention kernel is launched on), or None."""
+    @contextmanager
+    def _span(self, rows, batch):
+        """While self._events is a list: HIP events on the current stream (the one the attention kernel is launched
+        on) around a self-attention launch, appended to it; `rows` of the `batch` CFG rows ran in the span."""
         if self._events is None:
-            return None
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        return ev
-
-    def _record_span(self, ev0, rows, batch):
-        """close a self-attention span opened by _record_event; `rows` of the `batch` CFG rows ran in it"""
-        if ev0 is None:
+            yield
             return
-        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        yield
         ev1.record()
         self._events.append((ev0, ev1, rows / batch))
+
+    # ------------------------------------------------------------------ the parts of a forward
+
+    def _patch_embed(self, f, lat, y, frame_offset, broadcast):
+        """patch embedding (1B:972-983): im2col + GEMM, padding rows zero; with SP every rank embeds
+        the whole sequence (the vocal projector reads it, 1B:1004-1009) and keeps its chunk (1B:1019).  Returns the
+        whole sequence's embedding [B * Lp, dim] fp32 (without SP the residual stream itself)."""
+        pk, ws, dev, B, Lp, Lc, dim = f.pk, f.ws, f.dev, f.B, f.Lp, f.Lc, self.dim
+        Fw, Hh, Ww = f.fhw
+        real = math.prod(f.grid)
+        cols = torch.empty(B, Lp, pk.kpad, device=dev, dtype=torch.bfloat16)
+        ops.patch_im2col(lat, y, B, Fw, Hh, Ww, cols, pk.kpad, Lp, x_frame_offset=frame_offset,
+                         x_batch_broadcast=broadcast)
+        xfull = ws.x if not self._sp_enabled else torch.empty(B * Lp, dim, device=dev, dtype=torch.float32)
+        call_gemm_batched(cols, pk.w_pe, pk.b_pe, xfull, B, real, Lp, dim, pk.kpad)
+        if real < Lp:
+            for b in range(B):
+                ops.fill_(xfull[b * Lp + real:(b + 1) * Lp], 0.0)
+        if self._sp_enabled:
+            ws.x.view(B, Lc, dim).copy_(xfull.view(B, Lp, dim)[:, f.rank * Lc:(f.rank + 1) * Lc])
+        return xfull
+
+    def _time_modulation(self, f, t):
+        """time embedding (fp32, 1B:986-990).  Returns e [B, dim], e0 [B, 6, dim], the blocks' modulation
+        [layers, B, 6, dim] and the head's [1, B, 2, dim]."""
+        pk, dev, B, dim = f.pk, f.dev, f.B, self.dim
+        tt = t.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if tt.numel() == 1:
+            tt = tt.expand(B).contiguous()
+        sin = torch.empty(B, self.freq_dim, device=dev, dtype=torch.float32)
+        ops.timestep_embed(tt, self.freq_dim, sin)
+        h1 = torch.empty(B, dim, device=dev, dtype=torch.float32)
+        ops.small_linear_f32(sin, pk.w_te0, pk.b_te0, h1, act_out=1)
+        e = torch.empty(B, dim, device=dev, dtype=torch.float32)
+        ops.small_linear_f32(h1, pk.w_te2, pk.b_te2, e)
+        e0 = torch.empty(B, 6 * dim, device=dev, dtype=torch.float32)
+        ops.small_linear_f32(e, pk.w_tp, pk.b_tp, e0, act_in=1)
+        e0 = e0.view(B, 6, dim)
+        emod = torch.empty(self.num_layers, B, 6, dim, device=dev, dtype=torch.float32)
+        ops.mod_add(pk.mod, e0, emod)
+        hmod = torch.empty(1, B, 2, dim, device=dev, dtype=torch.float32)
+        ops.mod_add(pk.head_mod, e, hmod, e_jstride=0)
+        return e, e0, emod, hmod
+
+    def _vocal_context(self, f, xfull, vocal_embeddings, n_video_frames, e0, e):
+        """vocal context (1B:1004-1009) and every block's per-frame vocal K|V of it; sets f.n_fr, f.G (latent frames,
+        tokens per frame), f.nper (context rows per frame) and f.kvv."""
+        pk, dev, B, S, Lp, Lc, rank, dim = f.pk, f.dev, f.B, f.S, f.Lp, f.Lc, f.rank, self.dim
+        n_fr = (n_video_frames - 1) // 4 + 1
+        if S % n_fr:
+            raise ValueError("seq_len must split evenly into latent frames for the per-frame audio attention")
+        G = S // n_fr
+        # the latent frames this rank's tokens belong to (SP pads past S join the last frame): the only vocal
+        # context rows its cross-attention reads (sp.vocal_segments); without SP every frame
+        if self._sp_enabled:
+            t0, t1 = rank * Lc, min((rank + 1) * Lc, S)
+            vf0 = min(t0 // G, n_fr - 1)
+            vnf = min(max(t1 - 1, t0) // G, n_fr - 1) - vf0 + 1
+        else:
+            vf0, vnf = 0, n_fr
+        lat_row = torch.empty(vnf * G, dim, device=dev, dtype=torch.bfloat16)
+        if vocal_embeddings.shape[0] == 1 and B != 1:
+            raise ValueError("a single audio row drives a batch of 1 (1B:1008-1009); CFG batches pass 3 rows")
+        # 1.3B: the projector runs on the last (full-condition) row only, the unconditional row gets
+        # zeros (1B:1004-1009); 14B: every row through the projector with its own audio (14B:1008)
+        rows_v = B if (self.VOCAL == "14B" or vocal_embeddings.shape[0] == 1) else 1
+        voc_rows = []
+        for r in range(rows_v):
+            src = B - 1 if rows_v == 1 else r
+            ops.cast_bf16(xfull[src * Lp + vf0 * G:src * Lp + (vf0 + vnf) * G], lat_row)
+            vv, Fn, nper = self._vocal(pk, vocal_embeddings[src], n_video_frames, lat_row, S, e0[src:src + 1],
+                                       e[src:src + 1], frames=(vf0, vnf))
+            if self.vd != dim:
+                raise ValueError("vocal context width must equal the DiT width")
+            voc_rows.append(vv)
+        assert Fn == n_fr
+        vr = slice(vf0 * nper, (vf0 + vnf) * nper)  # the computed frames' rows of each CFG row's context
+        if rows_v == 1 and vnf == n_fr:
+            vctx = torch.zeros(B, Fn * nper, dim, device=dev, dtype=torch.bfloat16)
+            for b in range(1, B):
+                vctx[b].copy_(voc_rows[0])
+        elif vnf == n_fr:
+            vctx = torch.stack(voc_rows)
+        else:
+            vctx = torch.zeros(B, Fn * nper, dim, device=dev, dtype=torch.bfloat16)
+            for b in range(B):
+                if rows_v == B or b >= 1:
+                    vctx[b, vr].copy_(voc_rows[b if rows_v == B else 0])
+        vctx = vctx.view(B * Fn * nper, dim)
+        # per-frame vocal K|V of every block in one GEMM [B * n_fr * nper, layers * 2 * dim] (1B:575-578: the
+        # block's k_vocal / v_vocal of the shared vocal context); under SP only the rows of the frames this rank's
+        # queries read (the others are never read)
+        kvv_all = torch.empty(B * n_fr * nper, pk.w_kv_v_all.shape[0], device=dev, dtype=torch.bfloat16)
+        if vnf == n_fr:
+            ops.linear(vctx, pk.w_kv_v_all, pk.b_kv_v_all, ops.EPI_BF16, out=kvv_all)
+        else:
+            for b in range(B):
+                r0 = b * n_fr * nper + vf0 * nper
+                ops.linear(vctx[r0:r0 + vnf * nper], pk.w_kv_v_all, pk.b_kv_v_all, ops.EPI_BF16,
+                           out=kvv_all[r0:r0 + vnf * nper])
+        f.n_fr, f.G, f.nper = n_fr, G, nper
+        f.kvv = [kvv_all[:, 2 * dim * i:2 * dim * (i + 1)] for i in range(self.num_layers)]  # each block's k | v
+
+    def _plan_blocks(self, f, shared):
+        """The tables and the schedule of the layer loop.  Under sequence parallelism: the exchange (f.ex, f.omap,
+        f.pack_kw, f.k, f.v; f.Lq, f.hg become this rank's query part and head group) and its schedule (f.schedule,
+        with f.streams and f.main for the per-row streams).  f.all and f.row[b]: the workspace views of all CFG rows
+        and of row b, with their segment tables (a row's where the schedule launches it alone); f.use_cross3,
+        f.use_vt; f.dedup: the CFG rows are equal (`shared`) and the first block's self-attention half runs once."""
+        dev, B, S, Lp, Lc, rank, ctx, n_fr, nper = f.dev, f.B, f.S, f.Lp, f.Lc, f.rank, f.ctx, f.n_fr, f.nper
+        tl, ni, get, ws = ctx.text_len, ctx.img_len, self._segs.get, f.ws
+
+        def views(rows):  # the workspace rows of the CFG rows `rows`, sliced once per forward
+            rs = slice(rows.start * Lc, rows.stop * Lc)
+            return SimpleNamespace(rows=rows, x=ws.x[rs], mod=ws.mod[rs], qkv=ws.qkv[rs], att=ws.att[rs],
+                                   ffn=ws.ffn[rs], modq=ws.modq[rs] if hasattr(ws, "modq") else None)
+        f.all, f.row = views(range(B)), [views(range(b, b + 1)) for b in range(B)]
+        if self._sp_enabled:
+            plan = sp.make_plan(f.NS, rank, self.num_heads)
+            ex = f.ex = self._sp_exchange(plan, B, Lc, dev)
+            f.Lq, f.hg, f.omap = plan.G * Lc, plan.hg, ex.omap
+            f.k, f.v = ex.kv[:, :plan.hg * self.d], ex.kv[:, plan.hg * self.d:]
+            f.pack_kw = dict(table=ex.table, G=plan.G, R=plan.R, my_part=plan.part)
+            gpu = dev.type == "cuda"
+            f.schedule = sp_schedule(os.environ.get("SA_SP_OVERLAP", "1"), B, -(-f.Lq // 256) * f.hg,
+                                     ops._n_cu(dev) if gpu else 256, gpu)
+            if f.schedule == SP_STREAMS:
+                f.streams, f.main = self._row_streams(B, dev), torch.cuda.current_stream(dev)
+        # shared rows: the single-GPU layout, or the one-stream and per-row-stream Ulysses schedules
+        f.dedup = shared and B > 1 and f.schedule in (None, SP_BATCHED, SP_STREAMS)
+        # self-attention keys: the S tokens of the single-GPU sequence (the SP pads past S are queries only, their
+        # outputs are never read), so any degree reproduces the single-GPU forward
+        Lq, self_rows = f.Lq, [[b * f.Lq, f.Lq, b * Lp, S] for b in range(B)]
+        voc_list = sp.vocal_segments(B, S, Lc, rank, n_fr, nper)
+        vars(f.all).update(self_attn=get(("self", B, Lp, Lq, S), self_rows, dev),
+                           txt=get(("txt", B, Lc, tl), sp.local_segments(B, Lc, tl), dev),
+                           img=get(("img", B, Lc, ni), sp.local_segments(B, Lc, ni), dev),
+                           voc=get(("voc", B, S, Lc, rank, n_fr, nper), voc_list, dev),
+                           voc_n=len(voc_list), voc_q=max(s_[1] for s_ in voc_list))
+        for b, t in enumerate(f.row[:B if f.schedule in (SP_ROWS, SP_STREAMS) else int(f.dedup)]):
+            t.self_attn = get(("self_row", b, Lp, Lq, S), self_rows[b:b + 1], dev)
+            if f.schedule == SP_STREAMS:
+                # the row's cross-attention tables (query rows relative to the row's chunk, key rows absolute in the
+                # shared text / image / vocal K|V buffers) for the three-launch path
+                vl = [[q0 - b * Lc, ql, k0, kl] for q0, ql, k0, kl in voc_list if b * Lc <= q0 < (b + 1) * Lc]
+                t.txt = get(("rtxt", b, Lc, tl), [[0, Lc, b * tl, tl]], dev)
+                t.img = get(("rimg", b, Lc, ni), [[0, Lc, b * ni, ni]], dev)
+                t.voc = get(("rvoc", b, Lc, tuple(map(tuple, vl))), vl, dev)
+                t.voc_n, t.voc_q = len(vl), max(s_[1] for s_ in vl)
+        f.use_cross3 = (ni > 0 and f.G % 256 == 0 and (rank * Lc) % 256 == 0 and (rank + 1) * Lc <= S
+                        and os.environ.get("SA_CROSS3", "1") != "0")
+        f.use_vt = not self._sp_enabled and not self._fp8_attn and not self._fp8_qkv and self._vt_attention(Lp, dev)
+        if f.use_vt and f.ws.vt is None:
+            # zero-filled once: the pad columns past B * Lp are read (as P = 0 keys) by a partial last block, which
+            # stages a whole 64-key block: up to (B-1)*Lp + ceil64(Lp) <= ceil64(M) + 64 columns
+            f.ws.vt = torch.zeros(self.dim, (f.ws.x.shape[0] + 63) // 64 * 64 + 64, device=dev, dtype=torch.bfloat16)
+
+    def _head(self, f, hm, out):
+        """head (1B:715-723) + unpatchify (1B:1161-1184)"""
+        ws, B, Lc = f.ws, f.B, f.Lc
+        Fw, Hh, Ww = f.fhw
+        ops.layernorm_mod(ws.x, ws.mod, self.eps, shift=hm[:, 0], scale=hm[:, 1], rows_per_batch=Lc)
+        ho = ops.linear(ws.mod, f.pk.w_head, f.pk.b_head, ops.EPI_BF16)
+        if self._sp_enabled:  # every rank gets the whole prediction (1B:1150-1152)
+            ho = sp.gather_tokens(ho, B, Lc, f.NS, self.sp_group)
+        if out is None:
+            out = torch.empty(B, self.out_dim, Fw, Hh, Ww, device=f.dev, dtype=torch.bfloat16)
+        ops.unpatchify(ho, f.Lp, B, self.out_dim, Fw, Hh, Ww, out)
+        return out
 
     # ------------------------------------------------------------------ forward
 
@@ -908,290 +1156,40 @@ class WanTransformer3DFantasyModel(nn.Module):
         if y is not None and y.dtype != torch.bfloat16:
             y = y.to(torch.bfloat16)
         pk = self._pack()
-        dev = pk.w_pe.device
-        dim, H_ = self.dim, self.num_heads
+        dev, d = pk.w_pe.device, self.d
         Fw = y.shape[2] if y is not None else lat.shape[2] - frame_offset
         Hh, Ww = lat.shape[3], lat.shape[4]
-        hp, wp = Hh // 2, Ww // 2
-        real = Fw * hp * wp
-        NS, rank = self.sp_world_size, self.sp_world_rank
-        SP = self._sp_enabled  # sequence-parallel path (NS ranks; at NS = 1 no transfer, the same kernels)
+        grid = (Fw, Hh // 2, Ww // 2)
+        NS, rank = self.sp_world_size, self.sp_world_rank  # at NS = 1 the SP path has no transfer, the same kernels
         S = int(seq_len)  # the single-GPU sequence (1B:983): these keys are attended, SP's extra pads are not
         Lp = sp.padded_len(S, NS)
-        assert real <= S, "seq_len smaller than the token count"
+        assert math.prod(grid) <= S, "seq_len smaller than the token count"
         Lc = Lp // NS  # tokens of each CFG row held by this rank (all of them without SP)
-        ws = self._workspace(B * Lc, dev)
+        # the forward's state: what every step of every layer needs and no layer changes (_vocal_context adds the
+        # vocal K|V and frame geometry, _plan_blocks the tables and the schedule); Lq, hg: the whole row's at first
+        f = SimpleNamespace(
+            pk=pk, ws=self._workspace(B * Lc, dev), dev=dev, B=B, S=S, Lp=Lp, Lc=Lc, NS=NS, rank=rank,
+            fhw=(Fw, Hh, Ww), grid=grid,
+            rope_kw=dict(rope=pk.rope, rows_per_batch=Lc, tok_offset=rank * Lc, grid=grid, head_dim=d,
+                         n_frame_pairs=d // 2 - 2 * (d // 6), n_height_pairs=d // 6),
+            ex=None, omap=None, schedule=None, Lq=Lp, hg=self.num_heads)
 
-        # patch embedding (1B:972-983): im2col + GEMM, padding rows zero; with SP every rank embeds
-        # the whole sequence (the vocal projector reads it, 1B:1004-1009) and keeps its chunk (1B:1019)
-        cols = torch.empty(B, Lp, pk.kpad, device=dev, dtype=torch.bfloat16)
-        ops.patch_im2col(lat, y, B, Fw, Hh, Ww, cols, pk.kpad, Lp, x_frame_offset=frame_offset,
-                         x_batch_broadcast=broadcast)
-        xfull = ws.x if not SP else torch.empty(B * Lp, dim, device=dev, dtype=torch.float32)
-        call_gemm_batched(cols, pk.w_pe, pk.b_pe, xfull, B, real, Lp, dim, pk.kpad)
-        if real < Lp:
-            for b in range(B):
-                ops.fill_(xfull[b * Lp + real:(b + 1) * Lp], 0.0)
-        if SP:
-            ws.x.view(B, Lc, dim).copy_(xfull.view(B, Lp, dim)[:, rank * Lc:(rank + 1) * Lc])
-
-        # time embedding (fp32, 1B:986-990)
-        tt = t.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if tt.numel() == 1:
-            tt = tt.expand(B).contiguous()
-        sin = torch.empty(B, self.freq_dim, device=dev, dtype=torch.float32)
-        ops.timestep_embed(tt, self.freq_dim, sin)
-        h1 = torch.empty(B, dim, device=dev, dtype=torch.float32)
-        ops.small_linear_f32(sin, pk.w_te0, pk.b_te0, h1, act_out=1)
-        e = torch.empty(B, dim, device=dev, dtype=torch.float32)
-        ops.small_linear_f32(h1, pk.w_te2, pk.b_te2, e)
-        e0 = torch.empty(B, 6 * dim, device=dev, dtype=torch.float32)
-        ops.small_linear_f32(e, pk.w_tp, pk.b_tp, e0, act_in=1)
-        e0 = e0.view(B, 6, dim)
-        emod = torch.empty(self.num_layers, B, 6, dim, device=dev, dtype=torch.float32)
-        ops.mod_add(pk.mod, e0, emod)
-        hmod = torch.empty(1, B, 2, dim, device=dev, dtype=torch.float32)
-        ops.mod_add(pk.head_mod, e, hmod, e_jstride=0)
-
-        ctx = self._context(pk, context, clip_fea, B, dev)
-
+        xfull = self._patch_embed(f, lat, y, frame_offset, broadcast)
+        e, e0, emod, hmod = self._time_modulation(f, t)
+        f.ctx = self._context(pk, context, clip_fea, B, dev)
         # TeaCache (1B:1021-1044): optional, decided on e0 before any block work
         tc = self.teacache
-        x = ws.x
-        should_calc = True if tc is None else tc.decide(e0, cond_flag)
-        if not should_calc:  # 1B:1048-1050: reuse the last computed residual
-            ws.x.add_(tc.residual(cond_flag, dev))
+        if tc is not None and not tc.decide(e0, cond_flag):  # 1B:1048-1050: reuse the last computed residual
+            f.ws.x.add_(tc.residual(cond_flag, dev))
         else:
-            x_in = ws.x.clone() if tc is not None else None
-            # vocal context (1B:1004-1009): projector on the last (full-condition) row only
-            n_fr = (video_sample_n_frames - 1) // 4 + 1
-            if S % n_fr:
-                raise ValueError("seq_len must split evenly into latent frames for the per-frame audio attention")
-            G = S // n_fr
-            # the latent frames this rank's tokens belong to (SP pads past S join the last frame): the only vocal
-            # context rows its cross-attention reads (sp.vocal_segments); without SP every frame
-            if SP:
-                t0, t1 = rank * Lc, min((rank + 1) * Lc, S)
-                vf0 = min(t0 // G, n_fr - 1)
-                vnf = min(max(t1 - 1, t0) // G, n_fr - 1) - vf0 + 1
-            else:
-                vf0, vnf = 0, n_fr
-            lat_row = torch.empty(vnf * G, dim, device=dev, dtype=torch.bfloat16)
-            if vocal_embeddings.shape[0] == 1 and B != 1:
-                raise ValueError("a single audio row drives a batch of 1 (1B:1008-1009); CFG batches pass 3 rows")
-            # 1.3B: the projector runs on the last (full-condition) row only, the unconditional row gets
-            # zeros (1B:1004-1009); 14B: every row through the projector with its own audio (14B:1008)
-            rows_v = B if (self.VOCAL == "14B" or vocal_embeddings.shape[0] == 1) else 1
-            voc_rows = []
-            for r in range(rows_v):
-                src = B - 1 if rows_v == 1 else r
-                ops.cast_bf16(xfull[src * Lp + vf0 * G:src * Lp + (vf0 + vnf) * G], lat_row)
-                vv, Fn, nper = self._vocal(pk, vocal_embeddings[src], video_sample_n_frames, lat_row, S,
-                                           e0[src:src + 1], e[src:src + 1], dev, frames=(vf0, vnf))
-                if self.vd != dim:
-                    raise ValueError("vocal context width must equal the DiT width")
-                voc_rows.append(vv)
-            assert Fn == n_fr
-            vr = slice(vf0 * nper, (vf0 + vnf) * nper)  # the computed frames' rows of each CFG row's context
-            if rows_v == 1 and vnf == n_fr:
-                vctx = torch.zeros(B, Fn * nper, dim, device=dev, dtype=torch.bfloat16)
-                for b in range(1, B):
-                    vctx[b].copy_(voc_rows[0])
-            elif vnf == n_fr:
-                vctx = torch.stack(voc_rows)
-            else:
-                vctx = torch.zeros(B, Fn * nper, dim, device=dev, dtype=torch.bfloat16)
-                for b in range(B):
-                    if rows_v == B or b >= 1:
-                        vctx[b, vr].copy_(voc_rows[b if rows_v == B else 0])
-            vctx = vctx.view(B * Fn * nper, dim)
-
-            if SP:
-                plan = sp.make_plan(NS, rank, H_)
-                ex = self._sp_exchange(plan, B, Lc, dev)
-                Lq, hg, hgd = plan.G * Lc, plan.hg, plan.hg * self.d
-                pack_kw = dict(table=ex.table, G=plan.G, R=plan.R, my_part=plan.part)
-                # keys: the S tokens of the single-GPU sequence (the SP pads past S are queries only, their
-                # outputs are never read), so any degree reproduces the single-GPU forward
-                segs_self = self._segs.get(("self_sp", B, Lp, Lq, S), [[b * Lq, Lq, b * Lp, S] for b in range(B)],
-                                           dev)
-                # exchange schedule (SA_SP_OVERLAP: 0 one synchronous batched exchange per direction; 2 per-row
-                # exchanges and per-row attention; 3 per-row Q/K/V exchanges, batched attention; 1 = auto:
-                # 2 when per-row attention launches add no waves over the CUs -- a row's launch has ceil(Lq /
-                # 256) x hg workgroups and B serial launches must not need more rounds than the batched one --
-                # else 3 (N = 8: 63 workgroups per row would leave most CUs idle, but the Q/K/V exchange of
-                # row b can still travel under the QKV GEMMs of rows b+1..; per-row GEMMs there take as many
-                # rounds over the CUs as the batched one)
-                n_cu = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
-                wg_row = -(-Lq // 256) * hg
-                ov = os.environ.get("SA_SP_OVERLAP", "1")
-                if ov == "1" and B > 1 and dev.type == "cuda":
-                    # one stream per CFG row through the whole block: its compute alone matches the best of the
-                    # other schedules at every degree (per-rank forward with the transfers stubbed out, N = 2 / 4 / 8:
-                    # 197.2 / 103.3 / 59.3 ms vs 198.5 / 103.8 / 59.0 ms, profiles/r04/sp_rank_compute_r4s.jsonl)
-                    # and every transfer travels under the other rows' work
-                    ov = "4"
-                elif ov == "1":
-                    ov = "2" if B * -(-wg_row // n_cu) <= -(-(B * wg_row) // n_cu) else "3"
-                sp_rows, sp_rows_x = ov == "2", ov == "3" and B > 1
-                sp_streams = ov == "4" and B > 1 and dev.type == "cuda"
-                if sp_rows or sp_streams:
-                    segs_rows = [self._segs.get(("self_sp_row", b, Lp, Lq, S), [[b * Lq, Lq, b * Lp, S]], dev)
-                                 for b in range(B)]
-            else:
-                sp_rows = sp_rows_x = sp_streams = False
-                segs_self = self._segs.get(("self", B, Lp), [[b * Lp, Lp, b * Lp, Lp] for b in range(B)], dev)
-            segs_txt = self._segs.get(("txt", B, Lc, ctx.text_len), sp.local_segments(B, Lc, ctx.text_len), dev)
-            segs_img = self._segs.get(("img", B, Lc, ctx.img_len), sp.local_segments(B, Lc, ctx.img_len), dev)
-            voc_list = sp.vocal_segments(B, S, Lc, rank, n_fr, nper)
-            segs_voc = self._segs.get(("voc", B, S, Lc, rank, n_fr, nper), voc_list, dev)
-            voc_n, voc_q = len(voc_list), max(s_[1] for s_ in voc_list)
-            use_cross3 = (ctx.img_len > 0 and G % 256 == 0 and (rank * Lc) % 256 == 0 and (rank + 1) * Lc <= S
-                          and os.environ.get("SA_CROSS3", "1") != "0")
-            x = ws.x
-            use_vt = not SP and not self._fp8_attn and not self._fp8_qkv and self._vt_attention(Lp, dev)
-            # shared_rows: the first block's self-attention half once (single-GPU layout, or the one-stream and
-            # per-row-stream Ulysses schedules)
-            dedup = shared_rows and broadcast and B > 1 and (not SP or sp_streams or not (sp_rows or sp_rows_x))
-            if use_vt and ws.vt is None:
-                # zero-filled once: the pad columns past B * Lp are read (as P = 0 keys) by a partial last block, which
-                # stages a whole 64-key block: up to (B-1)*Lp + ceil64(Lp) <= ceil64(M) + 64 columns
-                ws.vt = torch.zeros(dim, (ws.x.shape[0] + 63) // 64 * 64 + 64, device=dev, dtype=torch.bfloat16)
-            # per-frame vocal K|V of every block in one GEMM [B * n_fr * nper, layers * 2 * dim] (1B:575-578: the
-            # block's k_vocal / v_vocal of the shared vocal context); under SP only the rows of the frames this rank's
-            # queries read (the others are never read)
-            kvv_all = torch.empty(B * n_fr * nper, pk.w_kv_v_all.shape[0], device=dev, dtype=torch.bfloat16)
-            if vnf == n_fr:
-                ops.linear(vctx, pk.w_kv_v_all, pk.b_kv_v_all, ops.EPI_BF16, out=kvv_all)
-            else:
-                for b in range(B):
-                    r0 = b * n_fr * nper + vf0 * nper
-                    ops.linear(vctx[r0:r0 + vnf * nper], pk.w_kv_v_all, pk.b_kv_v_all, ops.EPI_BF16,
-                               out=kvv_all[r0:r0 + vnf * nper])
-            grid = (Fw, hp, wp)
-            if sp_streams:
-                # every CFG row through the whole layer on its own HIP stream (_sp_layer_rows); rows are independent
-                rstreams = self._row_streams(B, dev)
-                main = torch.cuda.current_stream(dev)
-                for rs_ in rstreams:
-                    rs_.wait_stream(main)
-                row_segs = self._row_cross_segs(B, Lc, ctx, voc_list, dev)
-            for li, L in enumerate(pk.layers):
-                kvv = kvv_all[:, 2 * dim * li:2 * dim * (li + 1)]
-                em = emod[li]  # [B, 6, dim]
-                rope_kw = dict(rope=pk.rope, rows_per_batch=Lc, tok_offset=rank * Lc, grid=grid, head_dim=self.d,
-                               n_frame_pairs=self.d // 2 - 2 * (self.d // 6), n_height_pairs=self.d // 6)
-                first_shared = li == 0 and dedup
-                if first_shared:
-                    # the CFG rows enter the first block identical (shared_rows): its self-attention half for
-                    # row 0 only, then the residual stream copied to the other rows
-                    if SP:
-                        seg0 = self._segs.get(("self_sp_row", 0, Lp, Lq, S), [[0, Lq, 0, S]], dev)
-                        self._sp_self_attention_row0(L, x, ws, em, ex, pack_kw, rope_kw, Lc, Lq, hg, hgd, seg0, B)
-                        if sp_streams:
-                            for rs_ in rstreams:
-                                rs_.wait_stream(main)
-                    else:
-                        self._self_attention_rows(pk, L, x, ws, em, 1, Lc, Lp, use_vt, rope_kw, dev, batch=B)
-                        for b in range(1, B):
-                            x[b * Lc:(b + 1) * Lc].copy_(x[:Lc])
-                if sp_streams:
-                    self._sp_layer_rows(pk, L, li, x, ws, em, ex, pack_kw, rank, Lc, Lq, hg, hgd, grid,
-                                        segs_rows, row_segs, ctx, kvv, nper, G, n_fr, use_cross3, rstreams,
-                                        sa=not first_shared)
-                    continue
-                if not first_shared:  # self-attention (1B:675-679)
-                    self._norm1(x, ws, slice(None), em[:, 0], em[:, 1], Lc)
-                    if SP and sp_rows:
-                        # Ulysses pipelined over the CFG rows: row b's Q/K/V exchange is issued right after its
-                        # QKV GEMM + pack (so it travels under rows b+1..'s GEMMs), row b's attention waits
-                        # only on it, and row b's output exchange travels under the next rows' attention and
-                        # the earlier rows' O-projections
-                        pend = []
-                        for b in range(B):
-                            rs = slice(b * Lc, (b + 1) * Lc)
-                            self._qkv(L, x[rs], ws, rs, None, None, Lc, normed=True)
-                            ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, self.eps, b_offset=b, **pack_kw, **rope_kw)
-                            pend.append(ex.heads([b]))
-                        back = []
-                        for b in range(B):
-                            pend[b].wait()
-                            ev0 = self._record_event()
-                            self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_rows[b], 1, Lq,
-                                            hg, kernel=self.attn_kernel, o_rows=ex.omap)
-                            self._record_span(ev0, rows=1, batch=B)
-                            back.append(ex.tokens([b]))
-                        for b in range(B):
-                            rs = slice(b * Lc, (b + 1) * Lc)
-                            back[b].wait()
-                            a0, pnl = ex.panels(range(b, b + 1))
-                            ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=x[rs], residual=x[rs],
-                                       gate=em[b:b + 1, 2], rows_per_batch=Lc, a_panels=pnl)
-                    elif SP:
-                        if sp_rows_x:
-                            # per-row Q/K/V exchanges issued as each row's QKV GEMM + pack lands (they travel
-                            # under the later rows' GEMMs), one batched attention once all have arrived
-                            pend = []
-                            for b in range(B):
-                                rs = slice(b * Lc, (b + 1) * Lc)
-                                self._qkv(L, x[rs], ws, rs, None, None, Lc, normed=True)
-                                ops.qkv_pack(ws.qkv[rs], L.nq, L.nk, dim, self.eps, b_offset=b, **pack_kw, **rope_kw)
-                                pend.append(ex.heads([b]))
-                            for p_ in pend:
-                                p_.wait()
-                        else:  # one exchange per direction for all rows
-                            self._qkv(L, x, ws, slice(None), None, None, Lc, normed=True)
-                            ops.qkv_pack(ws.qkv, L.nq, L.nk, dim, self.eps, **pack_kw, **rope_kw)
-                            ex.heads(range(B)).wait()
-                        # Ulysses: full-sequence attention of this rank's (query part, head group), outputs written
-                        # to the owners' send slabs / this rank's own O-projection panel, then heads -> tokens
-                        ev0 = self._record_event()
-                        split = ops.attn_tail_split(0, B * hg * -(-Lq // 256), dev) if self.attn_kernel == 0 else 0
-                        self._self_attn(ws, ex.q, ex.kv[:, :hgd], ex.kv[:, hgd:], ex.obuf, segs_self, B, Lq, hg,
-                                        kernel=self.attn_kernel, o_rows=ex.omap, split_tiles=split)
-                        self._record_span(ev0, rows=B, batch=B)
-                        ex.tokens(range(B)).wait()
-                        a0, pnl = ex.panels()
-                        ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=x, residual=x, gate=em[:, 2],
-                                   rows_per_batch=Lc, a_panels=pnl)
-                    else:
-                        self._self_attention_rows(pk, L, x, ws, em, B, Lc, Lp, use_vt, rope_kw, dev, batch=B,
-                                                  normed=True)
-                # cross-attention: text + image + per-frame vocal (1B:534-605, 684)
-                ops.layernorm_mod(x, ws.mod, self.eps, weight=L.n3w, bias=L.n3b)
-                qc = ws.qkv[:, :dim]
-                ops.linear(ws.mod, L.w_cq, L.b_cq, ops.EPI_BF16, out=qc)
-                ops.qk_rmsnorm_rope(qc, 0, -1, L.cnq, None, dim, self.eps)
-                kvt, kvi = ctx.kv[li]
-                if use_cross3:  # text + image + vocal in one launch, bf16 sum as 1B:602
-                    ops.attention_cross3(qc, kvt[:, :dim], kvt[:, dim:], ctx.text_len, kvi[:, :dim], kvi[:, dim:],
-                                         ctx.img_len, kvv[:, :dim], kvv[:, dim:], nper, G, n_fr, ws.att, B, Lc, H_,
-                                         tok_offset=rank * Lc)
-                else:
-                    ops.attention(qc, kvt[:, :dim], kvt[:, dim:], ws.att, segs_txt, B, Lc, H_)
-                    if kvi is not None:
-                        ops.attention(qc, kvi[:, :dim], kvi[:, dim:], ws.att, segs_img, B, Lc, H_, accumulate=True)
-                    ops.attention(qc, kvv[:, :dim], kvv[:, dim:], ws.att, segs_voc, voc_n, voc_q, H_, accumulate=True)
-                ops.linear(ws.att, L.w_co, L.b_co, ops.EPI_RES_F32, out=x, residual=x)
-                # FFN (1B:687-691)
-                self._ffn(L, x, ws, slice(None), em[:, 3], em[:, 4], em[:, 5], Lc)
-            if sp_streams:
-                for rs_ in rstreams:
-                    main.wait_stream(rs_)
+            x_in = f.ws.x.clone() if tc is not None else None
+            self._vocal_context(f, xfull, vocal_embeddings, video_sample_n_frames, e0, e)
+            self._plan_blocks(f, shared_rows and broadcast)
+            self._blocks(f, emod)
             if tc is not None:  # 1B:1096-1099
-                tc.store(ws.x - x_in, cond_flag)
+                tc.store(f.ws.x - x_in, cond_flag)
                 del x_in
-
-        # head (1B:715-723) + unpatchify (1B:1161-1184)
-        hm = hmod[0]
-        ops.layernorm_mod(x, ws.mod, self.eps, shift=hm[:, 0], scale=hm[:, 1], rows_per_batch=Lc)
-        ho = ops.linear(ws.mod, pk.w_head, pk.b_head, ops.EPI_BF16)
-        if SP:  # every rank gets the whole prediction (1B:1150-1152)
-            ho = sp.gather_tokens(ho, B, Lc, NS, self.sp_group)
-        if out is None:
-            out = torch.empty(B, self.out_dim, Fw, Hh, Ww, device=dev, dtype=torch.bfloat16)
-        ops.unpatchify(ho, Lp, B, self.out_dim, Fw, Hh, Ww, out)
-        return out
+        return self._head(f, hmod[0], out)
 
 
 class WanTransformer3DFantasy14BModel(WanTransformer3DFantasyModel):

@@ -317,7 +317,7 @@ def _sp_worker(rank, world, port, qret):
 
 @pytest.mark.timeout(300)
 def test_sp_world2_fp8_attention():
-    """gloo world 2 sharing the GPU, the default exchange schedule (per-row streams: _sp_layer_rows), as
+    """gloo world 2 sharing the GPU, the default exchange schedule (per-row streams: _sp_block_streams), as
     tests/test_gpu_mxfp8.py::test_sp_world2_fp8_ffn drives it"""
     from test_gpu_sp import _rendezvous_file
     world = 2

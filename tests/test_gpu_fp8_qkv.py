@@ -298,7 +298,7 @@ def _sp_worker(rank, world, port, qret):
 
 @pytest.mark.timeout(300)
 def test_sp_world2_fp8_qkv_with_fp8_attention():
-    """gloo world 2 sharing the GPU, the default exchange schedule (per-row streams: _sp_layer_rows), as
+    """gloo world 2 sharing the GPU, the default exchange schedule (per-row streams: _sp_block_streams), as
     tests/test_gpu_fp8_attn.py::test_sp_world2_fp8_attention drives it: the sequence-parallel sites use the mode for
     the GEMM only, and the output is bit-identical to the single-GPU (fused) one"""
     from test_gpu_sp import _rendezvous_file
