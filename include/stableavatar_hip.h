@@ -207,6 +207,21 @@ int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales, int64_t l
                      const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel, int workgroups,
                      void* stream);
 
+/* sa_gemm_mxfp8_ex with the K step of the one-tile kernel chosen by the caller; every output and scale byte is the
+ * same under either step.  kstep: 0 = auto, resolved per launch (step 2 from 64 K-tiles on, K >= 8192, step 1 below;
+ * the environment variable SA_MXGEMM_KSTEP=1|2, read once per process, overrides auto only, and a persistent
+ * selection, explicit or through SA_MXGEMM_KERNEL=2, keeps step 1),
+ * 1 = the one-barrier step (the call is then sa_gemm_mxfp8_ex), 2 = one tile per workgroup with the DMA of K-tile
+ * t + 2 issued between the MFMAs of step t into the regions the step has read, and a counted vmcnt at the step's end;
+ * any other value is rejected.  kstep 2 takes kernel 0 or 1 and workgroups 0: kernel 2 or a grid cap with it is
+ * rejected.  sa_gemm_mxfp8 and sa_gemm_mxfp8_ex(kernel = 0) are this call with kstep = 0; sa_gemm_mxfp8_ex with an
+ * explicit kernel is this call with kstep = 1.  Every argument is checked before the first HIP call. */
+int sa_gemm_mxfp8_ks(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W, int64_t ldw,
+                     const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc, void* C_scales,
+                     int64_t ldcs, int M, int N, int K, int epilogue, const float* residual, int64_t ldr,
+                     const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel, int workgroups,
+                     int kstep, void* stream);
+
 /* ---- MXFP8 self-attention (opt-in fp8 attention mode; no counterpart in the reference) ----
  * WanSelfAttention's attention (wan_fantasy_transformer3d_1B.py:383-413) with both products on MXFP8 operands.
  * stableavatar_amd/mxfp8_attn.py is the definition.  head_dim 128 only.  segs is sa_attn_fwd's table

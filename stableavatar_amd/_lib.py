@@ -28,6 +28,7 @@ SIGNATURES = {
     "sa_layernorm_mod_mxfp8": "pliplplppppliiifp",
     "sa_gemm_mxfp8": "plplplplpplpliiiiplplip",
     "sa_gemm_mxfp8_ex": "plplplplpplpliiiiplpliiip",
+    "sa_gemm_mxfp8_ks": "plplplplpplpliiiiplpliiiip",
     "sa_attn_kmean":"plpiiippp",
     "sa_attn_pack_mxfp8": "plplplppiiiiifppppppplp",
     "sa_attn_fwd_mxfp8": "pppppplplppiiiipp",

@@ -17,6 +17,9 @@
 // each lane holds 4 consecutive output columns of one row.
 // gemm_mxp_kernel (sa_gemm_mxfp8_ex, kernel 2): the same tile and K step, one workgroup walking several tiles and
 // loading its next tile's first K-tile under the current tile's epilogue; the same bytes (its header, below).
+// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): the same tile, one per workgroup, on a K step that issues K-tile t + 2's
+// DMA pieces between the MFMAs of step t into the regions of the stage step t has read (four barriers per step) and ends
+// on a counted vmcnt; the same bytes (its header, below).  Auto picks it from 64 K-tiles on (the DiT's FFN-down).
 //
 // sa_gemm_mxfp8_vt (the V projection of the fp8 q/k/v mode, feeding sa_attn_fwd_mxfp8): the same K loop with the
 // operands NOT swapped (C = A·W^T; the product of two operand rows does not depend on which side they sit, so the
@@ -606,6 +609,174 @@ __global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
   }
 }
 
+// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): gemm_mx_kernel's tile, lane map, operand swap, staging image, raster and
+// clamped loads, one tile per workgroup, with a K step that issues no DMA burst and ends on a counted vmcnt.  A wave's
+// 18 DMA pieces of a K-tile are numbered 0-7 = its W pieces (half 2 + p / 4, piece p % 4), 8, 9 = the A and W scale
+// dwords, 10-13 = A rows 0-63 of both halves, 14-17 = A rows 64-127 of both halves.  Step t multiplies K-tile t out of
+// stage S = t & 1 while K-tile t + 1 lands in stage S ^ 1 and K-tile t + 2 is issued into stage S, region by region as
+// the step's reads free it (MFMA slot s = 8 m + n, row-major over the wave's 8 x 8 fragment tiles):
+//   top         34 LDS reads (8 W fragments, 16 scale dwords, A row 0)  -> lgkmcnt(0), barrier #1: W and scales free
+//   slots 0-19  pieces 0-9 (W, scales) of K-tile t + 2, one after every second MFMA from slot 1
+//   slot 24     A row 3 has been read (row m + 1 is read under row m's MFMAs) -> barrier #2: A rows 0-63 free
+//   slots 26-38 pieces 10-13, one after every fourth MFMA
+//   slot 56     A row 7 has been read                                         -> barrier #3: A rows 64-127 free
+//   slots 56-62 pieces 14-17, one after every second MFMA
+//   end         vmcnt(18): K-tile t + 1 has landed, K-tile t + 2's 18 pieces stay in flight -> barrier #4
+// With no K-tile t + 2 (the last two steps; every step of nk = 1, 2) nothing is issued and the step ends on vmcnt(0).
+// The prologue issues K-tiles 0 and 1 (K-tile 0 alone when nk = 1) and waits as a step's end does.  STAGE = 1 is the
+// first stage of that schedule, kept for measurement (SA_MXGEMM_KSTEP_STAGE): one barrier per step as gemm_mx_kernel,
+// K-tile t + 1's pieces issued one after every third MFMA from slot 2, vmcnt(0) at the end.
+// Each accumulator adds K-tiles 0 .. nk - 1 in order, one MFMA each, and the epilogue is mxp_epilogue, so every output
+// and scale byte equals gemm_mx_kernel's.  The step is one copy under one loop: the branch around a piece tests a
+// condition the compiler cannot relate to the next piece's, so it has no reason to duplicate the MFMAs between them.
+// Barriers: one before the loop and four (STAGE 1: one) per K step, all under the bound t < nk alone.
+template <int STAGE>
+constexpr int mxk_piece_after(int s) {
+  if (STAGE == 1) return (s >= 2 && (s - 2) % 3 == 0 && s < 56) ? (s - 2) / 3 : -1;
+  if (s < 20) return (s & 1) ? s / 2 : -1;
+  if (s >= 26 && s <= 38) return (s - 26) % 4 == 0 ? 10 + (s - 26) / 4 : -1;
+  if (s >= 56) return (s & 1) ? -1 : 14 + (s - 56) / 2;
+  return -1;
+}
+
+template <int EPI, int STAGE>
+__global__ __launch_bounds__(256) void gemm_mxk_kernel(MxArgs g) {
+  static_assert(STAGE == 1 || STAGE == 2, "K-step stage: 1 = interleaved issue, 2 = two tiles in flight");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fc = lane >> 4;
+  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
+  const int wg = xcd_remap(blockIdx.x, nm * nn);
+  int mt, nt;
+  tile_coords(wg, nm, nn, g.group_m, mt, nt);
+  const int m0 = mt * BM, n0 = nt * BN;
+  const int nk = g.K / BKB;
+
+  // gemm_mx_kernel's staging: rows past M / N clamped to the last row, so every load stays inside the operand
+  int goff[4][4];
+#pragma unroll
+  for (int h = 0; h < 4; ++h)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = (i * 4 + wave) * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      if (h < 2)
+        goff[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
+      else
+        goff[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
+    }
+  const int soff_a = min(m0 + tid, g.M - 1) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+  // piece P (the header's numbering) of K-tile kt < nk into ring stage kt & 1
+  auto dma = [&](auto pc, int kt) {
+    constexpr int P = pc.value;
+    if constexpr (P == 8 || P == 9) {
+      char* dst = smem + LDS_BYTES + (kt & 1) * SCALE_STAGE + (P - 8) * 1024 + wave * 256;
+      __builtin_amdgcn_global_load_lds((const void*)((P == 8 ? g.SA + soff_a : g.SW + soff_w) + kt * 4), LDS_PTR(dst), 4,
+                                       0, 0);
+    } else {
+      constexpr int q = P < 8 ? P : (P - 10) & 3;
+      constexpr int h = P < 8 ? 2 + q / 4 : q >> 1, i = P < 8 ? q % 4 : (P < 14 ? 0 : 2) + (q & 1);
+      __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + goff[h][i] + (long)kt * BKB),
+                                       LDS_PTR(smem + (kt & 1) * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024),
+                                       16, 0, 0);
+    }
+  };
+
+  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
+  const uint32_t swz = (fr >> 1) & 7;
+  const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
+  const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
+  const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
+  const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
+  const int sh = 8 * fc;
+  f32x4 acc[8][8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  unroll<18>([&](auto p) { dma(p, 0); });
+  if (STAGE == 2 && nk > 1) {
+    unroll<18>([&](auto p) { dma(p, 1); });
+    asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  for (int t = 0; t < nk; ++t) {
+    // K-tile t has landed in every wave's sight (the wait and barrier that ended step t - 1, or the prologue's)
+    const int kt = t + STAGE;  // the K-tile this step fetches
+    const bool more = kt < nk;
+    const uint32_t so = (t & 1) * STAGE_BYTES, ss = (t & 1) * SCALE_STAGE;
+    u32x4 bl[8], bh[8], al[2], ah[2];
+    uint32_t sar[8], swr[8];
+    unroll<8>([&](auto n) {
+      mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
+      mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
+      mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
+      mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
+    });
+    mx_ds<0>(al[0], a_lo + so);
+    mx_ds<0>(ah[0], a_hi + so);
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
+                   "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
+                   "+v"(al[0]), "+v"(ah[0])::"memory");
+    asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
+                      "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
+                      "+v"(swr[6]), "+v"(swr[7]));
+    if constexpr (STAGE == 2) {
+      // #1: every wave holds its W fragments and scales of stage t & 1
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    i32x8 b[8];
+    int sa[8], sw[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) {
+      b[n] = mx_join(bl[n], bh[n]);
+      sa[n] = (int)(sar[n] >> sh);
+      sw[n] = (int)(swr[n] >> sh);
+    }
+    unroll<8>([&](auto mc) {
+      constexpr int m = mc.value;
+      if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
+      if constexpr (m < 7) {
+        mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
+        mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
+      }
+      if constexpr (STAGE == 2 && (m == 3 || m == 7)) {
+        // #2, #3: every wave holds A rows 0-3 / 4-7 of its half (the read just issued at m = 3 is of row 4)
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
+      unroll<8>([&](auto nc) {
+        constexpr int n = nc.value, P = mxk_piece_after<STAGE>(m * 8 + n);
+        mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
+        if constexpr (P >= 0) {
+          int go = more;
+          asm volatile("" : "+v"(go));
+          if (__builtin_amdgcn_readfirstlane(go)) dma(std::integral_constant<int, P>{}, kt);
+        }
+      });
+    });
+    if (STAGE == 2 && more)
+      asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
+  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+  mxp_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
+}
+
 template <int EPI>
 int launch(const MxArgs& g, hipStream_t st) {
   static const bool attr = [] {
@@ -663,9 +834,52 @@ int launch_persistent(const MxArgs& g, int workgroups, hipStream_t st) {
   return SA_OK;
 }
 
+enum { KSTEP_AUTO = 0, KSTEP_ONE_BARRIER = 1, KSTEP_SPLIT = 2 };
+// what auto resolves to for the one-tile kernels (DESIGN.md "MXFP8 GEMM K step", Decision; bit-identical either way):
+// the default step, and the split step from SA_MXGEMM_KSTEP_SPLIT_MIN_NK K-tiles on -- the measured win is the 70-step
+// FFN-down tile; the 12-step tiles tie or lose
+#ifndef SA_MXGEMM_KSTEP_DEFAULT
+#define SA_MXGEMM_KSTEP_DEFAULT KSTEP_ONE_BARRIER
+#endif
+#ifndef SA_MXGEMM_KSTEP_SPLIT_MIN_NK
+#define SA_MXGEMM_KSTEP_SPLIT_MIN_NK 64
+#endif
+// which stage of the new step kstep 2 runs: 2 = the whole schedule, 1 = interleaved issue alone (measurement builds)
+#ifndef SA_MXGEMM_KSTEP_STAGE
+#define SA_MXGEMM_KSTEP_STAGE 2
+#endif
+
+// the K step auto picks for a launch of nk K-tiles (SA_MXGEMM_KSTEP=1|2 overrides, read once per process)
+int auto_kstep(int nk) {
+  static const int k = [] {
+    const char* e = getenv("SA_MXGEMM_KSTEP");
+    const int v = e ? atoi(e) : 0;
+    return (v == KSTEP_ONE_BARRIER || v == KSTEP_SPLIT) ? v : KSTEP_AUTO;
+  }();
+  if (k != KSTEP_AUTO) return k;
+  return nk >= SA_MXGEMM_KSTEP_SPLIT_MIN_NK ? KSTEP_SPLIT : SA_MXGEMM_KSTEP_DEFAULT;
+}
+
 template <int EPI>
-int launch_sel(const MxArgs& g, int kernel, int workgroups, hipStream_t st) {
-  if (kernel == KERNEL_AUTO) kernel = env_kernel();
+int launch_kstep(const MxArgs& g, hipStream_t st) {
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)gemm_mxk_kernel<EPI, SA_MXGEMM_KSTEP_STAGE>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    return true;
+  }();
+  (void)attr;
+  const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  hipLaunchKernelGGL((gemm_mxk_kernel<EPI, SA_MXGEMM_KSTEP_STAGE>), dim3(tiles), dim3(256), LDS_TOTAL, st, g);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+// auto, per launch: a persistent selection (explicit, or auto under SA_MXGEMM_KERNEL=2) keeps the one-barrier step
+template <int EPI>
+int launch_sel(const MxArgs& g, int kernel, int workgroups, int kstep, hipStream_t st) {
+  if (kernel == KERNEL_AUTO && kstep != KSTEP_SPLIT) kernel = env_kernel();
+  if (kstep == KSTEP_AUTO) kstep = kernel == KERNEL_PERSISTENT ? KSTEP_ONE_BARRIER : auto_kstep(g.K / BKB);
+  if (kstep == KSTEP_SPLIT) return launch_kstep<EPI>(g, st);
   return kernel == KERNEL_PERSISTENT ? launch_persistent<EPI>(g, workgroups, st) : launch<EPI>(g, st);
 }
 
@@ -710,12 +924,15 @@ extern "C" int sa_mxfp8_quant(const void* x, int64_t ldx, void* q, int64_t ldq, 
   return SA_OK;
 }
 
-extern "C" int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,
+extern "C" int sa_gemm_mxfp8_ks(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,
                                 int64_t ldw, const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
                                 void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
                                 int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel,
-                                int workgroups, void* stream) {
+                                int workgroups, int kstep, void* stream) {
   if (kernel < KERNEL_AUTO || kernel > KERNEL_PERSISTENT || workgroups < 0) return SA_ERR_ARG;
+  if (kstep < KSTEP_AUTO || kstep > KSTEP_SPLIT) return SA_ERR_ARG;
+  // the new step is a one-tile kernel: no persistent form, no grid cap
+  if (kstep == KSTEP_SPLIT && (kernel == KERNEL_PERSISTENT || workgroups != 0)) return SA_ERR_ARG;
   if (!A || !A_scales || !W || !W_scales || !C || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
   if (K % BKB != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 || ldws < K / 32)
     return SA_ERR_ARG;
@@ -736,11 +953,11 @@ extern "C" int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales
            rows_per_batch > 0 ? rows_per_batch : 1, M, N, K, epilogue == EPI_RES_F32 ? 4 : 8, M, 0};
   hipStream_t st = (hipStream_t)stream;
   switch (epilogue) {
-    case EPI_BF16: return launch_sel<EPI_BF16>(g, kernel, workgroups, st);
-    case EPI_GELU_BF16: return launch_sel<EPI_GELU_BF16>(g, kernel, workgroups, st);
-    case EPI_F32: return launch_sel<EPI_F32>(g, kernel, workgroups, st);
-    case EPI_RES_F32: return launch_sel<EPI_RES_F32>(g, kernel, workgroups, st);
-    case EPI_GELU_MXFP8: return launch_sel<EPI_GELU_MXFP8>(g, kernel, workgroups, st);
+    case EPI_BF16: return launch_sel<EPI_BF16>(g, kernel, workgroups, kstep, st);
+    case EPI_GELU_BF16: return launch_sel<EPI_GELU_BF16>(g, kernel, workgroups, kstep, st);
+    case EPI_F32: return launch_sel<EPI_F32>(g, kernel, workgroups, kstep, st);
+    case EPI_RES_F32: return launch_sel<EPI_RES_F32>(g, kernel, workgroups, kstep, st);
+    case EPI_GELU_MXFP8: return launch_sel<EPI_GELU_MXFP8>(g, kernel, workgroups, kstep, st);
     default: return SA_ERR_ARG;
   }
 }
@@ -749,8 +966,19 @@ extern "C" int sa_gemm_mxfp8(const void* A, int64_t lda, const void* A_scales, i
                              const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
                              void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
                              int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, void* stream) {
-  return sa_gemm_mxfp8_ex(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, bias, C, ldc, C_scales, ldcs, M, N, K, epilogue,
-                          residual, ldr, gate, gate_bstride, rows_per_batch, KERNEL_AUTO, 0, stream);
+  return sa_gemm_mxfp8_ks(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, bias, C, ldc, C_scales, ldcs, M, N, K, epilogue,
+                          residual, ldr, gate, gate_bstride, rows_per_batch, KERNEL_AUTO, 0, KSTEP_AUTO, stream);
+}
+
+extern "C" int sa_gemm_mxfp8_ex(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,
+                                int64_t ldw, const void* W_scales, int64_t ldws, const float* bias, void* C, int64_t ldc,
+                                void* C_scales, int64_t ldcs, int M, int N, int K, int epilogue, const float* residual,
+                                int64_t ldr, const float* gate, int64_t gate_bstride, int rows_per_batch, int kernel,
+                                int workgroups, void* stream) {
+  // an explicit kernel keeps the one-barrier step (kernel 1 is the baseline arm of every A/B); auto forwards auto
+  return sa_gemm_mxfp8_ks(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, bias, C, ldc, C_scales, ldcs, M, N, K, epilogue,
+                          residual, ldr, gate, gate_bstride, rows_per_batch, kernel, workgroups,
+                          kernel == KERNEL_AUTO ? KSTEP_AUTO : KSTEP_ONE_BARRIER, stream);
 }
 
 extern "C" int sa_gemm_mxfp8_vt(const void* A, int64_t lda, const void* A_scales, int64_t ldas, const void* W,

@@ -6,8 +6,9 @@ launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the wh
 on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (LayerNorm .. operands ready) in bf16, with the
 fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused;
 attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16.
-gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ex's one-tile kernel (the baseline arm) against its persistent kernel on their
-GEMM shapes, and ditfp8qkv has a variant that runs every MXFP8 GEMM of the forward on the persistent kernel."""
+gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ks's one-tile kernel (the baseline arm) against its persistent kernel and
+against the one-tile kernel with the split K step (kstep=2) on their GEMM shapes, and ditfp8qkv has
+variants that run every MXFP8 GEMM of the forward on the persistent kernel and on the one-barrier K step."""
 from __future__ import annotations
 
 import json
@@ -512,10 +513,12 @@ MXGEMM_QKV_SHAPES = (("qk", 64512, 3072, 1536, ops.EPI_BF16), ("qkv", 64512, 460
 
 
 def bench_mxgemm_kernels(shapes, rounds=5):
-    """sa_gemm_mxfp8_ex's one-tile kernel (kernel=1, the baseline arm) against its persistent kernel (kernel=2, one
-    workgroup per CU) on random MXFP8 operands, same process, interleaved rounds, median of `rounds` per arm, every
-    round kept, spread = (max - min) / median per arm, the graphics clock after each round.  ratio = one-tile ms /
-    persistent ms (> 1: the persistent kernel is faster); `identical`: the two outputs (and scales) byte for byte."""
+    """sa_gemm_mxfp8_ks's one-tile kernel with the one-barrier K step (kernel=1, kstep=1: the baseline arm) against its
+    persistent kernel (kernel=2, one workgroup per CU) and the one-tile kernel with the split K step (kernel=1, kstep=2)
+    on random MXFP8 operands, same process, interleaved rounds, median of `rounds` per arm, every round kept, spread =
+    (max - min) / median per arm, the graphics clock after each round.  ratio = one-tile ms / persistent ms and
+    kstep_ratio = one-tile ms / split-step ms (> 1: the other arm is faster); `identical`: the three outputs (and
+    scales) byte for byte."""
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     res = []
@@ -528,12 +531,13 @@ def bench_mxgemm_kernels(shapes, rounds=5):
             kw = dict(residual=torch.randn(M, N, device=dev, generator=g), gate=torch.randn(3, N, device=dev, generator=g),
                       rows_per_batch=M // 3)
         if epi == ops.EPI_GELU_TANH_MXFP8:
-            outs = {k: ops.Mx8.empty(M, N, dev) for k in (1, 2)}
+            outs = {k: ops.Mx8.empty(M, N, dev) for k in (1, 2, 3)}
         else:
             dt = torch.float32 if epi == ops.EPI_RES_F32 else torch.bfloat16
-            outs = {k: torch.empty(M, N, device=dev, dtype=dt) for k in (1, 2)}
-        fns = {"one_tile": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[1], kernel=1, **kw),
-               "persistent": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[2], kernel=2, **kw)}
+            outs = {k: torch.empty(M, N, device=dev, dtype=dt) for k in (1, 2, 3)}
+        fns = {"one_tile": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[1], kernel=1, kstep=1, **kw),
+               "persistent": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[2], kernel=2, **kw),
+               "kstep2": lambda: ops.linear_mxfp8(x, w, bias, epi, out=outs[3], kernel=1, kstep=2, **kw)}
         times, clocks = {n: [] for n in fns}, []
         for _ in range(rounds):
             for n, fn in fns.items():
@@ -541,9 +545,9 @@ def bench_mxgemm_kernels(shapes, rounds=5):
             clocks.append(_sclk_mhz())
         torch.cuda.synchronize()
         if epi == ops.EPI_GELU_TANH_MXFP8:
-            same = torch.equal(outs[1].q, outs[2].q) and torch.equal(outs[1].s, outs[2].s)
+            same = all(torch.equal(outs[1].q, outs[k].q) and torch.equal(outs[1].s, outs[k].s) for k in (2, 3))
         else:
-            same = torch.equal(outs[1], outs[2])
+            same = all(torch.equal(outs[1], outs[k]) for k in (2, 3))
         ms = {n: sorted(t)[len(t) // 2] for n, t in times.items()}
         r = {"kernel": f"mxgemm_{name}", "M": M, "N": N, "K": K, "epilogue": epi, "tiles": -(-M // 256) * -(-N // 256),
              "cus": ops._n_cu(x.q.device), "sclk_mhz": clocks, "identical": bool(same)}
@@ -553,6 +557,7 @@ def bench_mxgemm_kernels(shapes, rounds=5):
             r[f"{n}_rounds_ms"] = [round(t, 4) for t in times[n]]
             r[f"{n}_spread"] = round((max(times[n]) - min(times[n])) / ms[n], 4)
         r["ratio"] = round(ms["one_tile"] / ms["persistent"], 4)
+        r["kstep_ratio"] = round(ms["one_tile"] / ms["kstep2"], 4)
         res.append(r)
         print(json.dumps(r), flush=True)
         del x, w, outs, kw
@@ -711,8 +716,9 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
     and the rel-L2 between their outputs.  fp8_attn_ab: the same for enable_fp8_attention() off, on, and on together
     with enable_fp8_ffn() (three models on the same weights), each output's rel-L2 against off, the graphics clock
     after each round.  fp8_qkv_ab: four variants on the same weights -- off; attention + FFN; those + enable_fp8_qkv()
-    unfused; fused; and fused with the MXFP8 GEMMs on their persistent kernel -- each output's rel-L2 against off, whether
-    fused equals unfused, and persistent equals fused, byte for byte."""
+    unfused; fused; fused with the MXFP8 GEMMs on their persistent kernel; and fused with every MXFP8 GEMM on the
+    one-barrier K step -- each output's rel-L2 against off, whether fused equals unfused, and persistent and the
+    one-barrier step equal fused, byte for byte."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -788,21 +794,21 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
             if k != "attn_ffn":
                 modes[k].enable_fp8_qkv()
                 modes[k]._fp8_qkv_fused = k.endswith("_fused")
-        # the fused variant again with every sa_gemm_mxfp8_ex launch on the persistent kernel: what SA_MXGEMM_KERNEL=2
-        # does to a process (the variable is read once, so one process cannot hold both of its states)
+        # the fused variant again with every sa_gemm_mxfp8_ks launch on the persistent kernel (what SA_MXGEMM_KERNEL=2
+        # does to a process; the variable is read once, so one process cannot hold both of its states), and once more
+        # with every launch on the one-barrier K step (what SA_MXGEMM_KSTEP=1 does: the baseline arm of the K-step auto)
         import os
-        pers = "attn_ffn_qkv_fused_persistent"
-        modes[pers] = modes["attn_ffn_qkv_fused"]
+        pers, ks1 = "attn_ffn_qkv_fused_persistent", "attn_ffn_qkv_fused_kstep1"
+        modes[pers] = modes[ks1] = modes["attn_ffn_qkv_fused"]
         one_tile_or_auto = ops.linear_mxfp8
-
-        def persistent(*a, **kw):
-            return one_tile_or_auto(*a, **dict(kw, kernel=2))
+        forced = {pers: lambda *a, **kw: one_tile_or_auto(*a, **dict(kw, kernel=2)),
+                  ks1: lambda *a, **kw: one_tile_or_auto(*a, **dict(kw, kstep=1))}
         times, clocks, outs = {k: [] for k in modes}, [], {}
         with torch.no_grad():
             for _ in range(3):
                 for k, mm in modes.items():
                     f = lambda mm=mm: mm.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)  # noqa: E731
-                    ops.linear_mxfp8 = persistent if k == pers else one_tile_or_auto
+                    ops.linear_mxfp8 = forced.get(k, one_tile_or_auto)
                     try:
                         times[k].append(_time(f, iters=2, warmup=1))
                         outs[k] = f().float()
@@ -810,16 +816,19 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
                         ops.linear_mxfp8 = one_tile_or_auto
                 clocks.append(_sclk_mhz())
         r = {"kernel": "dit_forward_fp8_qkv_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks,
-             "SA_MXGEMM_KERNEL": os.environ.get("SA_MXGEMM_KERNEL"),
+             "SA_MXGEMM_KERNEL": os.environ.get("SA_MXGEMM_KERNEL"), "SA_MXGEMM_KSTEP": os.environ.get("SA_MXGEMM_KSTEP"),
              "fused_equals_unfused": bool(torch.equal(outs["attn_ffn_qkv_fused"], outs["attn_ffn_qkv_unfused"])),
-             "persistent_equals_fused": bool(torch.equal(outs[pers], outs["attn_ffn_qkv_fused"]))}
+             "persistent_equals_fused": bool(torch.equal(outs[pers], outs["attn_ffn_qkv_fused"])),
+             "kstep1_equals_fused": bool(torch.equal(outs[ks1], outs["attn_ffn_qkv_fused"])),
+             "rounds_ms": {k: [round(v, 2) for v in times[k]] for k in ("attn_ffn_qkv_fused", pers, ks1)}}
         for k in modes:
             r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
             if k != "off":
                 r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
                 r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
-        for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused", pers):
+        for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused", pers, ks1):
             r[f"ratio_{k}_vs_attn_ffn"] = round(r["attn_ffn_ms"] / r[f"{k}_ms"], 4)
+        r["ratio_kstep_auto_vs_kstep1"] = round(r[f"{ks1}_ms"] / r["attn_ffn_qkv_fused_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os

@@ -236,11 +236,12 @@ def layernorm_mod_mxfp8(x, out, eps, weight=None, bias=None, shift=None, scale=N
 
 
 def linear_mxfp8(x, weight, bias=None, epilogue=EPI_BF16, out=None, residual=None, gate=None, rows_per_batch=0,
-                 kernel=0, workgroups=0):
-    """y = epi(deq(x) @ deq(weight)^T + bias) on the block-scaled fp8 MFMA (sa_gemm_mxfp8_ex).  x: Mx8 [M, K],
+                 kernel=0, workgroups=0, kstep=0):
+    """y = epi(deq(x) @ deq(weight)^T + bias) on the block-scaled fp8 MFMA (sa_gemm_mxfp8_ks).  x: Mx8 [M, K],
     weight: Mx8 [N, K], K % 128 == 0.  epilogue: EPI_BF16 / EPI_GELU_TANH_BF16 / EPI_F32 / EPI_RES_F32 as linear(),
     or EPI_GELU_TANH_MXFP8 (out: Mx8 [M, N] = the bf16 GELU output quantised, N % 32 == 0).  kernel: 0 = auto,
-    1 = one tile per workgroup, 2 = persistent (the same bytes); workgroups > 0 caps the persistent grid (tests, A/B)."""
+    1 = one tile per workgroup, 2 = persistent (the same bytes); workgroups > 0 caps the persistent grid (tests, A/B);
+    kstep: 0 = auto, 1 = the one-barrier K step, 2 = the split step (one tile per workgroup; the same bytes)."""
     M, K = x.shape
     N = weight.shape[0]
     if weight.shape[1] != K:
@@ -268,9 +269,10 @@ def linear_mxfp8(x, weight, bias=None, epilogue=EPI_BF16, out=None, residual=Non
         if gate is not None:
             assert gate.dtype == torch.float32 and gate.stride(-1) == 1
             gstride = gate.stride(0)
-    call("sa_gemm_mxfp8_ex", x.q.data_ptr(), x.q.stride(0), x.s.data_ptr(), x.s.stride(0), weight.q.data_ptr(),
+    call("sa_gemm_mxfp8_ks", x.q.data_ptr(), x.q.stride(0), x.s.data_ptr(), x.s.stride(0), weight.q.data_ptr(),
          weight.q.stride(0), weight.s.data_ptr(), weight.s.stride(0), _p(bias), c.data_ptr(), c.stride(0), cs, cs_ld,
-         M, N, K, epilogue, _p(residual), ldr, _p(gate), gstride, rows_per_batch, kernel, workgroups, _stream())
+         M, N, K, epilogue, _p(residual), ldr, _p(gate), gstride, rows_per_batch, kernel, workgroups, kstep,
+         _stream())
     return out
 
 
