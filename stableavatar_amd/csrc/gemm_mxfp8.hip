@@ -6,20 +6,28 @@
 // v_mfma_scale_f32_16x16x128_f8f6f4.  Replaces, when the mode is on, the aten::addmm of the FFN
 // (wan_fantasy_transformer3d_1B.py:644-646 through :687-691), which has no fp8 counterpart in the reference.
 //
-// gemm_mx_kernel: 4 waves, one per SIMD, over a 256x256 tile (2 x 2 waves of 128 x 128, the 256 accumulators in
-// AGPRs, as gemm.hip's persistent kernel), K-tiles of 128 bytes staged by global_load ... lds into the bf16 kernels'
-// XOR-swizzled LDS image (a 128-element fp8 K-tile is the same 128 bytes per row as their 64 bf16), two 64-KB stages
-// (+ 2 KB of scale bytes each), one barrier per K step: tile t+1 lands while tile t multiplies.
+// Three kernels share one tile, one K step, one staging path and one row epilogue, each written once below:
+//   tile      4 waves, one per SIMD, over 256x256 (2 x 2 waves of 128 x 128, the 256 accumulators in AGPRs, as
+//             gemm.hip's persistent kernel), raster xcd_remap / tile_coords
+//   staging   mx_place / mx_dma / mx_dma_scale / mx_issue: K-tiles of 128 bytes by global_load ... lds into the bf16
+//             kernels' XOR-swizzled LDS image (a 128-element fp8 K-tile is the same 128 bytes per row as their 64
+//             bf16), two 64-KB stages (+ 2 KB of scale bytes each), rows past the operand clamped to its last row
+//   K step    mx_frag / mx_step: 34 LDS reads, then 8 x 8 scaled MFMAs with A row m + 1 read under row m's
+//   epilogue  mx_epilogue<EPI> (bias, GELU, bf16 / fp32 / gated residual / MXFP8 rows), mx_epilogue_vt (V^T)
 // Lane map of the scaled MFMA (established with the exact-integer test): lane l = (row r = l % 16, group g = l / 16)
 // supplies K bytes 16 g .. 16 g + 15 in its first four operand VGPRs and 64 + 16 g .. 64 + 16 g + 15 in the last
 // four (the 16-byte chunks g and 4 + g of the row -- the bf16 kernels' fragment addresses), and byte 0 of its scale
 // operand is the E8M0 scale of K block g (bytes 32 g .. 32 g + 31) of row r.  Operands are swapped (C^T = W·A^T) so
 // each lane holds 4 consecutive output columns of one row.
-// gemm_mxp_kernel (sa_gemm_mxfp8_ex, kernel 2): the same tile and K step, one workgroup walking several tiles and
-// loading its next tile's first K-tile under the current tile's epilogue; the same bytes (its header, below).
-// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): the same tile, one per workgroup, on a K step that issues K-tile t + 2's
-// DMA pieces between the MFMAs of step t into the regions of the stage step t has read (four barriers per step) and ends
-// on a counted vmcnt; the same bytes (its header, below).  Auto picks it from 64 K-tiles on (the DiT's FFN-down).
+// Each accumulator adds K-tiles 0 .. nk - 1 in order, one MFMA each, under every schedule, so the three kernels
+// write the same bytes.  What each adds to the shared pieces:
+// gemm_mx_kernel: one tile per workgroup, one barrier per K step: K-tile t + 1 is issued in one burst behind the
+// barrier and lands while K-tile t multiplies.  With EPI_VT it is sa_gemm_mxfp8_vt's kernel (below).
+// gemm_mxp_kernel (sa_gemm_mxfp8_ex, kernel 2): that step, one workgroup walking several tiles and loading its next
+// tile's first K-tile under the current tile's epilogue (its header, below).
+// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): one tile per workgroup on a K step that issues K-tile t + 2's DMA
+// pieces between the MFMAs of step t into the regions of the stage step t has read (four barriers per step) and ends
+// on a counted vmcnt (its header, below).  Auto picks it from 64 K-tiles on (the DiT's FFN-down).
 //
 // sa_gemm_mxfp8_vt (the V projection of the fp8 q/k/v mode, feeding sa_attn_fwd_mxfp8): the same K loop with the
 // operands NOT swapped (C = A·W^T; the product of two operand rows does not depend on which side they sit, so the
@@ -64,9 +72,6 @@ constexpr int LDS_BYTES = 2 * STAGE_BYTES;    // 128 KB
 constexpr int SCALE_STAGE = 2 * 256 * 4;      // 2 KB: a K-tile's scale dwords, A rows then W rows
 constexpr int LDS_TOTAL = LDS_BYTES + 2 * SCALE_STAGE;
 
-// byte offset of 16-byte chunk c of row r in a [rows][128 B] tile (gemm.hip's swz128)
-__device__ __forceinline__ int swz128(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
-
 // gemm.hip's tile raster: runs of gm tile rows, column-major inside a run
 __device__ __forceinline__ void tile_coords(int wg, int nm, int nn, int gm, int& mt, int& nt) {
   const int per = gm * nn;
@@ -105,29 +110,26 @@ __device__ __forceinline__ void mx_mma(f32x4& c, const i32x8& w, const i32x8& x,
                : "v"(w), "v"(x), "v"(sw), "v"(sa));
 }
 
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int fr = lane & 15, fc = lane >> 4;
-  constexpr bool VT = EPI == EPI_VT;
-  const int nm = VT ? (g.M / g.rows_per_seg) * g.seg_mt : (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
-  const int wg = xcd_remap(blockIdx.x, nm * nn);
-  int mt, nt;
-  tile_coords(wg, nm, nn, g.group_m, mt, nt);
-  // EPI_VT tiles the M axis per segment: tile mt is rows t0 .. t0 + 255 of segment sg (rows at or past rows_per_seg
-  // are clamped to the segment's last row on load and written as zeros)
-  const int sg = VT ? mt / g.seg_mt : 0, t0 = VT ? (mt % g.seg_mt) * BM : 0;
-  const int m0 = VT ? sg * g.rows_per_seg + t0 : mt * BM, n0 = nt * BN;
-  const int m_last = VT ? (sg + 1) * g.rows_per_seg - 1 : g.M - 1;  // the last row a load of this tile may touch
-  const int nk = g.K / BKB;
+__device__ __forceinline__ void mx_zero(f32x4 (&acc)[8][8]) {
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
 
-  // staging: half-tile h (0, 1 = A rows 0-127 / 128-255, 2, 3 = W) is 16 pieces of 1 KB (8 rows), four per wave;
-  // lane l of a piece writes LDS bytes 16 l.. and so reads row l / 8, chunk (l % 8) ^ swizzle.  Rows past M / N
-  // are clamped to the last row (read again, never stored), so every load stays inside the operand.
-  int goff[4][4];
+// Staging.  Half-tile h (0, 1 = A rows 0-127 / 128-255, 2, 3 = W) is 16 pieces of 1 KB (8 rows), four per wave (piece
+// i of a wave is piece 4 i + wave of the half); lane l of a piece writes LDS bytes 16 l.. and so reads row l / 8, chunk
+// (l % 8) ^ swizzle (gemm.hip's swz128).  The K-tile's scale bytes ride along: one dword (the tile's four K blocks)
+// per row, thread i fetching row i of the A and of the W tile into [256] dwords each behind the ring.
+// MxOff: a thread's byte offsets of K-tile 0 of one tile, 16 operand pieces and 2 scale rows.
+struct MxOff {
+  int g[4][4], sa, sw;
+};
+
+// the offsets of the tile at (m0, n0).  Rows past m_last / N - 1 are clamped to that row (read again, never stored),
+// so every load stays inside the operand; m_last is M - 1, or the last row of the tile's segment under EPI_VT
+__device__ __forceinline__ void mx_place(const MxArgs& g, int m0, int n0, int m_last, int wave, int tid, MxOff& o) {
+  const int lane = tid & 63;
 #pragma unroll
   for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -135,142 +137,124 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
       const int row = (i * 4 + wave) * 8 + (lane >> 3);
       const int chunk = (lane & 7) ^ ((row >> 1) & 7);
       if (h < 2)
-        goff[h][i] = min(m0 + h * 128 + row, m_last) * (int)g.lda + chunk * 16;
+        o.g[h][i] = min(m0 + h * 128 + row, m_last) * (int)g.lda + chunk * 16;
       else
-        goff[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
+        o.g[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
     }
-  auto issue = [&](int kt) {
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + goff[h][i] + (long)kt * BKB),
-                                         LDS_PTR(smem + (kt & 1) * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024),
-                                         16, 0, 0);
-  };
-  // the K-tile's scale bytes ride along: one dword (the tile's four K blocks) per row, thread i fetching row i of
-  // the A and of the W tile into [256] dwords each behind the ring
-  const int soff_a = min(m0 + tid, m_last) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
-  auto issue_scales = [&](int kt) {
-    char* dst = smem + LDS_BYTES + (kt & 1) * SCALE_STAGE + wave * 256;
-    __builtin_amdgcn_global_load_lds((const void*)(g.SA + soff_a + kt * 4), LDS_PTR(dst), 4, 0, 0);
-    __builtin_amdgcn_global_load_lds((const void*)(g.SW + soff_w + kt * 4), LDS_PTR(dst + 1024), 4, 0, 0);
-  };
+  o.sa = min(m0 + tid, m_last) * (int)g.ldsa;
+  o.sw = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+}
 
-  // per-lane fragment read bases: row m * 16 + fr of a half-tile, chunks fc and 4 + fc (swz128: the XOR term
-  // depends on fr only, so m is an immediate offset); the row's scale dword, byte fc of it shifted down to byte 0
+// piece I of half-tile H of K-tile kt into ring stage st
+template <int H, int I>
+__device__ __forceinline__ void mx_dma(const MxArgs& g, char* smem, const MxOff& o, int wave, int kt, int st) {
+  __builtin_amdgcn_global_load_lds((const void*)((H < 2 ? g.A : g.W) + o.g[H][I] + (long)kt * BKB),
+                                   LDS_PTR(smem + st * STAGE_BYTES + H * HALF_BYTES + (I * 4 + wave) * 1024), 16, 0, 0);
+}
+// K-tile kt's scale dword of the thread's A (SIDE 0) or W (SIDE 1) row into ring stage st
+template <int SIDE>
+__device__ __forceinline__ void mx_dma_scale(const MxArgs& g, char* smem, const MxOff& o, int wave, int kt, int st) {
+  __builtin_amdgcn_global_load_lds((const void*)((SIDE ? g.SW + o.sw : g.SA + o.sa) + kt * 4),
+                                   LDS_PTR(smem + LDS_BYTES + st * SCALE_STAGE + SIDE * 1024 + wave * 256), 4, 0, 0);
+}
+// the 18-piece burst: the operand pieces h-major, then the A and the W scales
+__device__ __forceinline__ void mx_issue(const MxArgs& g, char* smem, const MxOff& o, int wave, int kt, int st) {
+  unroll<16>([&](auto p) { mx_dma<p.value / 4, p.value % 4>(g, smem, o, wave, kt, st); });
+  mx_dma_scale<0>(g, smem, o, wave, kt, st);
+  mx_dma_scale<1>(g, smem, o, wave, kt, st);
+}
+
+// per-lane fragment read bases: row m * 16 + fr of a half-tile, chunks fc and 4 + fc (swz128: the XOR term
+// depends on fr only, so m is an immediate offset); the row's scale dword, byte fc of it shifted down to byte 0
+struct MxFrag {
+  uint32_t a_lo, a_hi, w_lo, w_hi, sa_rd, sw_rd;
+  int sh;
+};
+__device__ __forceinline__ MxFrag mx_frag(const char* smem, int wm, int wn, int fr, int fc) {
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
   const uint32_t swz = (fr >> 1) & 7;
-  const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
-  const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
-  const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
-  const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
-  const int sh = 8 * fc;
-  f32x4 acc[8][8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  MxFrag f;
+  f.a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
+  f.a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
+  f.w_lo = f.a_lo + (2 + wn - wm) * HALF_BYTES;
+  f.w_hi = f.a_hi + (2 + wn - wm) * HALF_BYTES;
+  f.sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4;
+  f.sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
+  f.sh = 8 * fc;
+  return f;
+}
 
-  issue(0);
-  issue_scales(0);
-  for (int t = 0; t < nk; ++t) {
-    // tile t has landed (every wave waits for its own pieces, then the barrier), and every wave is done reading
-    // the other stage (tile t - 1), which tile t + 1 now overwrites
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + 1 < nk) {
-      issue(t + 1);
-      issue_scales(t + 1);
-    }
-    // the W fragments, every scale and A row 0 first; then row m's 8 MFMAs run while row m + 1 is read
-    const uint32_t so = (t & 1) * STAGE_BYTES, ss = (t & 1) * SCALE_STAGE;
-    u32x4 bl[8], bh[8], al[2], ah[2];
-    uint32_t sar[8], swr[8];
-    unroll<8>([&](auto n) {
-      mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
-      mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
-      mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
-      mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
-    });
-    mx_ds<0>(al[0], a_lo + so);
-    mx_ds<0>(ah[0], a_hi + so);
-    // the wait "writes" every register the reads above fill, so nothing that uses them moves above it
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
-                   "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
-                   "+v"(al[0]), "+v"(ah[0])::"memory");
-    asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
-                      "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
-                      "+v"(swr[6]), "+v"(swr[7]));
-    i32x8 b[8];
-    int sa[8], sw[8];
+// One K step out of ring stage `stage`: the W fragments, every scale and A row 0 first; then row m's 8 MFMAs run
+// while row m + 1 is read.  VT: the operands not swapped (the file header).  The schedules hang their own work on
+// three callables: top() after the fragment wait, row(integral_constant m) after row m + 1's reads are issued,
+// slot(integral_constant 8 m + n) after each MFMA; empty lambdas leave the plain step.
+// The reads are asm the compiler does not count, so each wait "writes" every register the reads before it fill:
+// nothing that uses them moves above it.
+// The step is one body under one loop in every kernel: peeling a step out of the loop duplicated the body, and the
+// compiler moved accumulators between the two copies' register assignments right behind inline-asm MFMAs whose
+// latency it cannot see (wrong results, no fault).
+template <bool VT, class Top, class Row, class Slot>
+__device__ __forceinline__ void mx_step(f32x4 (&acc)[8][8], const MxFrag& f, int stage, Top&& top, Row&& row,
+                                        Slot&& slot) {
+  const uint32_t so = stage * STAGE_BYTES, ss = stage * SCALE_STAGE;
+  u32x4 bl[8], bh[8], al[2], ah[2];
+  uint32_t sar[8], swr[8];
+  unroll<8>([&](auto n) {
+    mx_ds<n.value * 2048>(bl[n.value], f.w_lo + so);
+    mx_ds<n.value * 2048>(bh[n.value], f.w_hi + so);
+    mx_ds32<n.value * 64>(swr[n.value], f.sw_rd + ss);
+    mx_ds32<n.value * 64>(sar[n.value], f.sa_rd + ss);
+  });
+  mx_ds<0>(al[0], f.a_lo + so);
+  mx_ds<0>(ah[0], f.a_hi + so);
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
+                 "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
+                 "+v"(al[0]), "+v"(ah[0])::"memory");
+  asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
+                    "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
+                    "+v"(swr[6]), "+v"(swr[7]));
+  top();
+  i32x8 b[8];
+  int sa[8], sw[8];
 #pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      b[n] = mx_join(bl[n], bh[n]);
-      sa[n] = (int)(sar[n] >> sh);
-      sw[n] = (int)(swr[n] >> sh);
-    }
-    unroll<8>([&](auto mc) {
-      constexpr int m = mc.value;
-      if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
-      if constexpr (m < 7) {
-        mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
-        mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
-      }
-      const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        if constexpr (VT)
-          mx_mma(acc[m][n], a, b[n], sa[m], sw[n]);
-        else
-          mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
-      }
-    });
+  for (int n = 0; n < 8; ++n) {
+    b[n] = mx_join(bl[n], bh[n]);
+    sa[n] = (int)(sar[n] >> f.sh);
+    sw[n] = (int)(swr[n] >> f.sh);
   }
-
-  // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-
-  if constexpr (VT) {
-    // V^T epilogue (lane map: the header): this wave's half is keys k0 .. k0 + 127 of segment sg, V^T columns
-    // vc .. vc + 127; a half that starts at or past the segment's end owns no columns and writes nothing
-    const int k0 = t0 + wm * 128, cw = n0 + wn * 128;
-    if (k0 >= g.rows_per_seg || cw >= g.N) return;
-    const long vc = (long)sg * ((g.rows_per_seg + 127) / 128 * 128) + k0;
-    uint8_t* Vq = (uint8_t*)g.C;
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      const int col = cw + n * 16 + fr;
-      const float bv = g.bias ? g.bias[col] : 0.f;
-#pragma unroll
-      for (int hi = 0; hi < 2; ++hi) {
-        float v[16];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            // the bf16 rounding of the Linear output (SA_EPI_BF16), keys past the segment as zeros
-            const bool live = k0 + 16 * (4 * hi + t) + 4 * fc + e < g.rows_per_seg;
-            v[4 * t + e] = live ? bf2f(f2bf(acc[4 * hi + t][n][e] + bv)) : 0.f;
-          }
-        float amax = fmaxf(mx_amax8(v), mx_amax8(v + 8));
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        uint32_t s;
-        const u32x2 lo = mx_quant8(v, amax, &s), hi2 = mx_quant8(v + 8, amax, &s);
-        *(u32x4*)(Vq + (long)col * g.ldc + vc + 64 * hi + 16 * fc) = (u32x4){lo[0], lo[1], hi2[0], hi2[1]};
-        if ((fc & 1) == 0) g.SC[(long)col * g.ldsc + vc / 32 + 2 * hi + (fc >> 1)] = (uint8_t)s;
-      }
+  unroll<8>([&](auto mc) {
+    constexpr int m = mc.value;
+    if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
+    if constexpr (m < 7) {
+      mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], f.a_lo + so);
+      mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], f.a_hi + so);
     }
-    return;
-  }
+    row(mc);
+    const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
+    unroll<8>([&](auto nc) {
+      constexpr int n = nc.value;
+      mx_mma(acc[m][n], VT ? a : b[n], VT ? b[n] : a, VT ? sa[m] : sw[n], VT ? sw[n] : sa[m]);
+      slot(std::integral_constant<int, 8 * m + n>{});
+    });
+  });
+}
 
-  // epilogue straight from the accumulators: acc[m][n] of lane (fr, fc) = row m0 + wm*128 + m*16 + fr, columns
-  // n0 + wn*128 + n*16 + 4 fc + 0..3.  Walked in column pairs (n = 2p, 2p + 1): the 32 columns of pair p in one row
-  // are one MXFP8 block, held by the four lanes fr, fr + 16, fr + 32, fr + 48.
+// the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
+__device__ __forceinline__ void mx_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
+
+// Row epilogue of the tile at (m0, n0), straight from the accumulators: acc[m][n] of lane (fr, fc) = row
+// m0 + wm*128 + m*16 + fr, columns n0 + wn*128 + n*16 + 4 fc + 0..3.  Walked in column pairs (n = 2p, 2p + 1): the 32
+// columns of pair p in one row are one MXFP8 block, held by the four lanes fr, fr + 16, fr + 32, fr + 48.
+template <int EPI>
+__device__ __forceinline__ void mx_epilogue(const MxArgs& g, f32x4 (&acc)[8][8], int m0, int n0, int wm, int wn,
+                                            int fr, int fc) {
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
+    // pair p's accumulators leave the AGPRs here, after pair p - 1's stores: read all at once (the compiler's choice
+    // when left free) the 256 of them fill the VGPR file and the gated-residual and MXFP8 epilogues spill
+#pragma unroll
+    for (int m = 0; m < 8; ++m) asm volatile("" : "+a"(acc[m][2 * p]), "+a"(acc[m][2 * p + 1])::"memory");
     const int cb = n0 + wn * 128 + p * 32;  // the block's first column (wave-uniform)
     if (cb >= g.N) continue;
     const int c[2] = {cb + 4 * fc, cb + 16 + 4 * fc};
@@ -359,173 +343,121 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
   }
 }
 
-// gemm_mxp_kernel's row epilogue for the tile at (m0, n0): gemm_mx_kernel's, statement for statement (a copy: sharing
-// one function between the two kernels rescheduled gemm_mx_kernel's scalar prologue, DESIGN.md "Persistent MXFP8 GEMM").
-// acc[m][n] of lane (fr, fc) = row m0 + wm*128 + m*16 + fr, columns n0 + wn*128 + n*16 + 4 fc + 0..3, walked in column
-// pairs (n = 2p, 2p + 1): the 32 columns of pair p in one row are one MXFP8 block, held by lanes fr, fr + 16, + 32, + 48.
-template <int EPI>
-__device__ __forceinline__ void mxp_epilogue(const MxArgs& g, f32x4 (&acc)[8][8], int m0, int n0, int wm, int wn,
-                                             int fr, int fc) {
+// V^T epilogue (lane map: the file header) of the tile at rows t0 .. t0 + 255 of segment sg, columns n0 ..: this wave's
+// half is keys k0 .. k0 + 127 of the segment, V^T columns vc .. vc + 127; a half that starts at or past the segment's
+// end owns no columns and writes nothing
+__device__ __forceinline__ void mx_epilogue_vt(const MxArgs& g, f32x4 (&acc)[8][8], int sg, int t0, int n0, int wm,
+                                               int wn, int fr, int fc) {
+  const int k0 = t0 + wm * 128, cw = n0 + wn * 128;
+  if (k0 >= g.rows_per_seg || cw >= g.N) return;
+  const long vc = (long)sg * ((g.rows_per_seg + 127) / 128 * 128) + k0;
+  uint8_t* Vq = (uint8_t*)g.C;
 #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    // pair p's accumulators leave the AGPRs here, after pair p - 1's stores: read all at once (the compiler's choice
-    // when left free) the 256 of them fill the VGPR file and the gated-residual and MXFP8 epilogues spill
+  for (int n = 0; n < 8; ++n) {
+    const int col = cw + n * 16 + fr;
+    const float bv = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) asm volatile("" : "+a"(acc[m][2 * p]), "+a"(acc[m][2 * p + 1])::"memory");
-    const int cb = n0 + wn * 128 + p * 32;  // the block's first column (wave-uniform)
-    if (cb >= g.N) continue;
-    const int c[2] = {cb + 4 * fc, cb + 16 + 4 * fc};
-    float bv[2][4];
+    for (int hi = 0; hi < 2; ++hi) {
+      float v[16];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+      for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bv[h][e] = (g.bias && c[h] + e < g.N) ? g.bias[c[h] + e] : 0.f;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int row = m0 + wm * 128 + m * 16 + fr;
-      const bool live = row < g.M;
-      float v[8];
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * h + e] = acc[m][2 * p + h][e] + bv[h][e];
-      if constexpr (EPI == EPI_GELU_BF16 || EPI == EPI_GELU_MXFP8) {
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          const bf16x2 hb = __builtin_convertvector((f32x2){v[j], v[j + 1]}, bf16x2);
-          const f32x2 y = gelu_tanh2(__builtin_convertvector(hb, f32x2));
-          v[j] = y[0];
-          v[j + 1] = y[1];
+        for (int e = 0; e < 4; ++e) {
+          // the bf16 rounding of the Linear output (SA_EPI_BF16), keys past the segment as zeros
+          const bool live = k0 + 16 * (4 * hi + t) + 4 * fc + e < g.rows_per_seg;
+          v[4 * t + e] = live ? bf2f(f2bf(acc[4 * hi + t][n][e] + bv)) : 0.f;
         }
-      }
-      if constexpr (EPI == EPI_GELU_MXFP8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(v[j]));
-        float amax = mx_amax8(v);
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        uint32_t s;
-        const u32x2 q = mx_quant8(v, amax, &s);
-        if (live) {
-          uint8_t* C = (uint8_t*)g.C + (long)row * g.ldc;
-          *(uint32_t*)(C + c[0]) = q[0];
-          *(uint32_t*)(C + c[1]) = q[1];
-          if (fc == 0) g.SC[(long)row * g.ldsc + cb / 32] = (uint8_t)s;
-        }
-      } else if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_BF16) {
-        if (live) {
-          bf16* C = (bf16*)g.C + (long)row * g.ldc;
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            if (c[h] + 4 <= g.N) {
-              *(bf16x4*)(C + c[h]) = (bf16x4){f2bf(v[4 * h]), f2bf(v[4 * h + 1]), f2bf(v[4 * h + 2]), f2bf(v[4 * h + 3])};
-            } else {
-              for (int e = 0; e < 4; ++e)
-                if (c[h] + e < g.N) C[c[h] + e] = f2bf(v[4 * h + e]);
-            }
-          }
-        }
-      } else {
-        if (live) {
-          float* C = (float*)g.C + (long)row * g.ldc;
-          const float* R = EPI == EPI_RES_F32 ? g.R + (long)row * g.ldr : nullptr;
-          const float* gt =
-              (EPI == EPI_RES_F32 && g.gate) ? g.gate + (long)(row / g.rows_per_batch) * g.gate_bstride : nullptr;
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            if (c[h] + 4 <= g.N) {
-              f32x4 o = {v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]};
-              if constexpr (EPI == EPI_RES_F32) {
-                const f32x4 r = *(const f32x4*)(R + c[h]);
-                const f32x4 gg = gt ? *(const f32x4*)(gt + c[h]) : (f32x4){1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = r[e] + bf2f(f2bf(o[e])) * gg[e];
-              }
-              *(f32x4*)(C + c[h]) = o;
-            } else {
-              for (int e = 0; e < 4; ++e)
-                if (c[h] + e < g.N) {
-                  float o = v[4 * h + e];
-                  if constexpr (EPI == EPI_RES_F32) o = R[c[h] + e] + bf2f(f2bf(o)) * (gt ? gt[c[h] + e] : 1.0f);
-                  C[c[h] + e] = o;
-                }
-            }
-          }
-        }
-      }
+      float amax = fmaxf(mx_amax8(v), mx_amax8(v + 8));
+      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+      uint32_t s;
+      const u32x2 lo = mx_quant8(v, amax, &s), hi2 = mx_quant8(v + 8, amax, &s);
+      *(u32x4*)(Vq + (long)col * g.ldc + vc + 64 * hi + 16 * fc) = (u32x4){lo[0], lo[1], hi2[0], hi2[1]};
+      if ((fc & 1) == 0) g.SC[(long)col * g.ldsc + vc / 32 + 2 * hi + (fc >> 1)] = (uint8_t)s;
     }
   }
 }
 
-// gemm_mxp_kernel: gemm_mx_kernel's tile, lane map, staging and K step, persistent over tiles.  Workgroup w of a grid of
-// G = min(tiles, workgroups) walks tiles w, w + G, ... of the xcd_remap / tile_coords order.  One running K-step counter
-// s gives the ring stage (s & 1), so a tile with an odd K-tile count hands the next tile the other stage.  During a
-// tile's last K step the free stage receives K-tile 0 (and its scales) of the workgroup's next tile, from load offsets
-// worked out in that step; those loads fly under the epilogue and the next tile's first step waits for them as any step
-// waits for its tile.  Each accumulator still adds K-tiles 0 .. nk - 1 in order, one MFMA each, so every output byte
-// equals gemm_mx_kernel's.
+// tiles of the M axis: per segment under EPI_VT (a segment's last tile may be partly live)
+__host__ __device__ __forceinline__ int mx_tiles_m(const MxArgs& g, bool vt) {
+  return vt ? (g.M / g.rows_per_seg) * g.seg_mt : (g.M + BM - 1) / BM;
+}
+__host__ __device__ __forceinline__ int mx_tiles(const MxArgs& g, bool vt = false) {
+  return mx_tiles_m(g, vt) * ((g.N + BN - 1) / BN);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fc = lane >> 4;
+  constexpr bool VT = EPI == EPI_VT;
+  const int nm = mx_tiles_m(g, VT), nn = (g.N + BN - 1) / BN;
+  int mt, nt;
+  tile_coords(xcd_remap(blockIdx.x, nm * nn), nm, nn, g.group_m, mt, nt);
+  // EPI_VT tiles the M axis per segment: tile mt is rows t0 .. t0 + 255 of segment sg (rows at or past rows_per_seg
+  // are clamped to the segment's last row on load and written as zeros)
+  const int sg = VT ? mt / g.seg_mt : 0, t0 = VT ? (mt % g.seg_mt) * BM : 0;
+  const int m0 = VT ? sg * g.rows_per_seg + t0 : mt * BM, n0 = nt * BN;
+  const int nk = g.K / BKB;
+  MxOff off;
+  mx_place(g, m0, n0, VT ? (sg + 1) * g.rows_per_seg - 1 : g.M - 1, wave, tid, off);
+  const MxFrag frag = mx_frag(smem, wm, wn, fr, fc);
+  f32x4 acc[8][8];
+  mx_zero(acc);
+
+  mx_issue(g, smem, off, wave, 0, 0);
+  for (int t = 0; t < nk; ++t) {
+    // tile t has landed (every wave waits for its own pieces, then the barrier), and every wave is done reading
+    // the other stage (tile t - 1), which tile t + 1 now overwrites
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 1 < nk) mx_issue(g, smem, off, wave, t + 1, (t + 1) & 1);
+    mx_step<VT>(acc, frag, t & 1, [] {}, [](auto) {}, [](auto) {});
+  }
+  mx_drain();
+  if constexpr (VT)
+    mx_epilogue_vt(g, acc, sg, t0, n0, wm, wn, fr, fc);
+  else
+    mx_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
+}
+
+// gemm_mxp_kernel: gemm_mx_kernel's step, persistent over tiles.  Workgroup w of a grid of G = min(tiles, workgroups)
+// walks tiles w, w + G, ... of the xcd_remap / tile_coords order.  One running K-step counter s gives the ring stage
+// (s & 1), so a tile with an odd K-tile count hands the next tile the other stage.  During a tile's last K step the
+// free stage receives K-tile 0 (and its scales) of the workgroup's next tile, from load offsets worked out in that
+// step; those loads fly under the epilogue and the next tile's first step waits for them as any step waits for its
+// tile.
 // Barriers: one per K step, under tile- and step-loop bounds that depend on blockIdx.x, gridDim.x and the tile count
 // only; a workgroup without a tile returns before the first.
-struct MxpOff {
-  int g[4][4], sa, sw;  // a tile's 16 operand pieces and 2 scale rows per thread: byte offsets of K-tile 0
-};
-
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN, total = nm * nn;
+  const int nm = mx_tiles_m(g, false), nn = (g.N + BN - 1) / BN, total = nm * nn;
   const int nk = g.K / BKB;
   const int G = gridDim.x;
   if ((int)blockIdx.x >= total) return;
 
-  // the load offsets of tile u (gemm_mx_kernel's staging: rows past M / N clamped to the last row)
-  auto place = [&](int u, int tid, MxpOff& o, int& m0, int& n0) {
-    const int lane = tid & 63;
+  // the load offsets of tile u
+  auto place = [&](int u, int tid, MxOff& o, int& m0, int& n0) {
     int mt, nt;
     tile_coords(xcd_remap(u, total), nm, nn, g.group_m, mt, nt);
     m0 = mt * BM;
     n0 = nt * BN;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = (i * 4 + wave) * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-        if (h < 2)
-          o.g[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
-        else
-          o.g[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
-      }
-    o.sa = min(m0 + tid, g.M - 1) * (int)g.ldsa;
-    o.sw = min(n0 + tid, g.N - 1) * (int)g.ldsw;
-  };
-  // K-tile kt of the placed tile and its scale dwords into ring stage st
-  auto issue = [&](const MxpOff& o, int kt, int st) {
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + o.g[h][i] + (long)kt * BKB),
-                                         LDS_PTR(smem + st * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024), 16,
-                                         0, 0);
-    char* dst = smem + LDS_BYTES + st * SCALE_STAGE + wave * 256;
-    __builtin_amdgcn_global_load_lds((const void*)(g.SA + o.sa + kt * 4), LDS_PTR(dst), 4, 0, 0);
-    __builtin_amdgcn_global_load_lds((const void*)(g.SW + o.sw + kt * 4), LDS_PTR(dst + 1024), 4, 0, 0);
+    mx_place(g, m0, n0, g.M - 1, wave, tid, o);
   };
 
   f32x4 acc[8][8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
+  mx_zero(acc);
   {
-    MxpOff first;
+    MxOff first;
     int m0, n0;
     place(blockIdx.x, threadIdx.x, first, m0, n0);
-    issue(first, 0, 0);
+    mx_issue(g, smem, first, wave, 0, 0);
   }
   int s = 0;  // K steps this workgroup has run, over all its tiles
   for (int u = blockIdx.x; u < total; u += G) {
@@ -535,14 +467,8 @@ __global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63, fr = lane & 15, fc = lane >> 4;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-    const uint32_t swz = (fr >> 1) & 7;
-    const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
-    const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
-    const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
-    const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
-    const int sh = 8 * fc;
-    MxpOff cur;
+    const MxFrag frag = mx_frag(smem, wm, wn, fr, fc);
+    MxOff cur;
     int m0, n0;
     place(u, tid, cur, m0, n0);
     for (int t = 0; t < nk; ++t, ++s) {
@@ -552,69 +478,29 @@ __global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       if (t + 1 < nk) {
-        issue(cur, t + 1, (s + 1) & 1);
+        mx_issue(g, smem, cur, wave, t + 1, (s + 1) & 1);
       } else if (u + G < total) {
         // the next tile's offsets live in this branch only: replacing `cur` here makes every step of the loop copy
         // and sign-extend all 18 of them (measured: 4 % on a 70-step tile); the next tile derives them again
-        MxpOff nxt;
+        MxOff nxt;
         int nm0, nn0;
         place(u + G, tid, nxt, nm0, nn0);
-        issue(nxt, 0, (s + 1) & 1);
+        mx_issue(g, smem, nxt, wave, 0, (s + 1) & 1);
       }
-      const uint32_t so = (s & 1) * STAGE_BYTES, ss = (s & 1) * SCALE_STAGE;
-      u32x4 bl[8], bh[8], al[2], ah[2];
-      uint32_t sar[8], swr[8];
-      unroll<8>([&](auto n) {
-        mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
-        mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
-        mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
-        mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
-      });
-      mx_ds<0>(al[0], a_lo + so);
-      mx_ds<0>(ah[0], a_hi + so);
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
-                     "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
-                     "+v"(al[0]), "+v"(ah[0])::"memory");
-      asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
-                        "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
-                        "+v"(swr[6]), "+v"(swr[7]));
-      i32x8 b[8];
-      int sa[8], sw[8];
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        b[n] = mx_join(bl[n], bh[n]);
-        sa[n] = (int)(sar[n] >> sh);
-        sw[n] = (int)(swr[n] >> sh);
-      }
-      unroll<8>([&](auto mc) {
-        constexpr int m = mc.value;
-        if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
-        if constexpr (m < 7) {
-          mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
-          mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
-        }
-        const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
-#pragma unroll
-        for (int n = 0; n < 8; ++n) mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
-      });
+      mx_step<false>(acc, frag, s & 1, [] {}, [](auto) {}, [](auto) {});
     }
-    // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    mxp_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-#pragma unroll
-      for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    mx_drain();
+    mx_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
+    mx_zero(acc);
   }
 }
 
-// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): gemm_mx_kernel's tile, lane map, operand swap, staging image, raster and
-// clamped loads, one tile per workgroup, with a K step that issues no DMA burst and ends on a counted vmcnt.  A wave's
-// 18 DMA pieces of a K-tile are numbered 0-7 = its W pieces (half 2 + p / 4, piece p % 4), 8, 9 = the A and W scale
-// dwords, 10-13 = A rows 0-63 of both halves, 14-17 = A rows 64-127 of both halves.  Step t multiplies K-tile t out of
-// stage S = t & 1 while K-tile t + 1 lands in stage S ^ 1 and K-tile t + 2 is issued into stage S, region by region as
-// the step's reads free it (MFMA slot s = 8 m + n, row-major over the wave's 8 x 8 fragment tiles):
+// gemm_mxk_kernel (sa_gemm_mxfp8_ks, kstep 2): one tile per workgroup, with a K step that issues no DMA burst and ends
+// on a counted vmcnt.  A wave's 18 DMA pieces of a K-tile are numbered 0-7 = its W pieces (half 2 + p / 4, piece
+// p % 4), 8, 9 = the A and W scale dwords, 10-13 = A rows 0-63 of both halves, 14-17 = A rows 64-127 of both halves.
+// Step t multiplies K-tile t out of stage S = t & 1 while K-tile t + 1 lands in stage S ^ 1 and K-tile t + 2 is issued
+// into stage S, region by region as the step's reads free it (MFMA slot s = 8 m + n, row-major over the wave's 8 x 8
+// fragment tiles), through mx_step's three callables:
 //   top         34 LDS reads (8 W fragments, 16 scale dwords, A row 0)  -> lgkmcnt(0), barrier #1: W and scales free
 //   slots 0-19  pieces 0-9 (W, scales) of K-tile t + 2, one after every second MFMA from slot 1
 //   slot 24     A row 3 has been read (row m + 1 is read under row m's MFMAs) -> barrier #2: A rows 0-63 free
@@ -626,9 +512,8 @@ __global__ __launch_bounds__(256) void gemm_mxp_kernel(MxArgs g) {
 // The prologue issues K-tiles 0 and 1 (K-tile 0 alone when nk = 1) and waits as a step's end does.  STAGE = 1 is the
 // first stage of that schedule, kept for measurement (SA_MXGEMM_KSTEP_STAGE): one barrier per step as gemm_mx_kernel,
 // K-tile t + 1's pieces issued one after every third MFMA from slot 2, vmcnt(0) at the end.
-// Each accumulator adds K-tiles 0 .. nk - 1 in order, one MFMA each, and the epilogue is mxp_epilogue, so every output
-// and scale byte equals gemm_mx_kernel's.  The step is one copy under one loop: the branch around a piece tests a
-// condition the compiler cannot relate to the next piece's, so it has no reason to duplicate the MFMAs between them.
+// The branch around a piece tests a condition the compiler cannot relate to the next piece's, so it has no reason to
+// duplicate the MFMAs between them (mx_step: one body under one loop).
 // Barriers: one before the loop and four (STAGE 1: one) per K step, all under the bound t < nk alone.
 template <int STAGE>
 constexpr int mxk_piece_after(int s) {
@@ -647,15 +532,15 @@ __global__ __launch_bounds__(256) void gemm_mxk_kernel(MxArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fc = lane >> 4;
-  const int nm = (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
-  const int wg = xcd_remap(blockIdx.x, nm * nn);
+  const int nm = mx_tiles_m(g, false), nn = (g.N + BN - 1) / BN;
   int mt, nt;
-  tile_coords(wg, nm, nn, g.group_m, mt, nt);
+  tile_coords(xcd_remap(blockIdx.x, nm * nn), nm, nn, g.group_m, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int nk = g.K / BKB;
-
-  // gemm_mx_kernel's staging: rows past M / N clamped to the last row, so every load stays inside the operand
-  int goff[4][4];
+  // mx_place's statements, kept inline in this kernel alone: behind the call the compiler forms each piece's address
+  // after the M0 write, right in front of the load, at all 16 operand sites between the MFMAs, and the step measured
+  // 0.6 - 0.7 % slower on the FFN shapes (DESIGN.md "MXFP8 GEMM K step", the fold)
+  MxOff off;
 #pragma unroll
   for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -663,39 +548,27 @@ __global__ __launch_bounds__(256) void gemm_mxk_kernel(MxArgs g) {
       const int row = (i * 4 + wave) * 8 + (lane >> 3);
       const int chunk = (lane & 7) ^ ((row >> 1) & 7);
       if (h < 2)
-        goff[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
+        off.g[h][i] = min(m0 + h * 128 + row, g.M - 1) * (int)g.lda + chunk * 16;
       else
-        goff[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
+        off.g[h][i] = min(n0 + (h - 2) * 128 + row, g.N - 1) * (int)g.ldw + chunk * 16;
     }
-  const int soff_a = min(m0 + tid, g.M - 1) * (int)g.ldsa, soff_w = min(n0 + tid, g.N - 1) * (int)g.ldsw;
+  off.sa = min(m0 + tid, g.M - 1) * (int)g.ldsa;
+  off.sw = min(n0 + tid, g.N - 1) * (int)g.ldsw;
   // piece P (the header's numbering) of K-tile kt < nk into ring stage kt & 1
   auto dma = [&](auto pc, int kt) {
-    constexpr int P = pc.value;
-    if constexpr (P == 8 || P == 9) {
-      char* dst = smem + LDS_BYTES + (kt & 1) * SCALE_STAGE + (P - 8) * 1024 + wave * 256;
-      __builtin_amdgcn_global_load_lds((const void*)((P == 8 ? g.SA + soff_a : g.SW + soff_w) + kt * 4), LDS_PTR(dst), 4,
-                                       0, 0);
-    } else {
-      constexpr int q = P < 8 ? P : (P - 10) & 3;
-      constexpr int h = P < 8 ? 2 + q / 4 : q >> 1, i = P < 8 ? q % 4 : (P < 14 ? 0 : 2) + (q & 1);
-      __builtin_amdgcn_global_load_lds((const void*)((h < 2 ? g.A : g.W) + goff[h][i] + (long)kt * BKB),
-                                       LDS_PTR(smem + (kt & 1) * STAGE_BYTES + h * HALF_BYTES + (i * 4 + wave) * 1024),
-                                       16, 0, 0);
-    }
+    constexpr int P = pc.value, q = P < 8 ? P : (P - 10) & 3;
+    if constexpr (P == 8 || P == 9)
+      mx_dma_scale<P - 8>(g, smem, off, wave, kt, kt & 1);
+    else
+      mx_dma<(P < 8 ? 2 + q / 4 : q >> 1), (P < 8 ? q % 4 : (P < 14 ? 0 : 2) + (q & 1))>(g, smem, off, wave, kt, kt & 1);
   };
-
-  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-  const uint32_t swz = (fr >> 1) & 7;
-  const uint32_t a_lo = lds0 + wm * HALF_BYTES + fr * 128 + ((fc ^ swz) << 4);
-  const uint32_t a_hi = lds0 + wm * HALF_BYTES + fr * 128 + (((4 + fc) ^ swz) << 4);
-  const uint32_t w_lo = a_lo + (2 + wn - wm) * HALF_BYTES, w_hi = a_hi + (2 + wn - wm) * HALF_BYTES;
-  const uint32_t sa_rd = lds0 + LDS_BYTES + (wm * 128 + fr) * 4, sw_rd = lds0 + LDS_BYTES + 1024 + (wn * 128 + fr) * 4;
-  const int sh = 8 * fc;
+  auto barrier = [] {
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  const MxFrag frag = mx_frag(smem, wm, wn, fr, fc);
   f32x4 acc[8][8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m)
-#pragma unroll
-    for (int n = 0; n < 8; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mx_zero(acc);
 
   unroll<18>([&](auto p) { dma(p, 0); });
   if (STAGE == 2 && nk > 1) {
@@ -704,88 +577,46 @@ __global__ __launch_bounds__(256) void gemm_mxk_kernel(MxArgs g) {
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
+  barrier();
   for (int t = 0; t < nk; ++t) {
     // K-tile t has landed in every wave's sight (the wait and barrier that ended step t - 1, or the prologue's)
     const int kt = t + STAGE;  // the K-tile this step fetches
     const bool more = kt < nk;
-    const uint32_t so = (t & 1) * STAGE_BYTES, ss = (t & 1) * SCALE_STAGE;
-    u32x4 bl[8], bh[8], al[2], ah[2];
-    uint32_t sar[8], swr[8];
-    unroll<8>([&](auto n) {
-      mx_ds<n.value * 2048>(bl[n.value], w_lo + so);
-      mx_ds<n.value * 2048>(bh[n.value], w_hi + so);
-      mx_ds32<n.value * 64>(swr[n.value], sw_rd + ss);
-      mx_ds32<n.value * 64>(sar[n.value], sa_rd + ss);
-    });
-    mx_ds<0>(al[0], a_lo + so);
-    mx_ds<0>(ah[0], a_hi + so);
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
-                   "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]),
-                   "+v"(al[0]), "+v"(ah[0])::"memory");
-    asm volatile("" : "+v"(sar[0]), "+v"(sar[1]), "+v"(sar[2]), "+v"(sar[3]), "+v"(sar[4]), "+v"(sar[5]), "+v"(sar[6]),
-                      "+v"(sar[7]), "+v"(swr[0]), "+v"(swr[1]), "+v"(swr[2]), "+v"(swr[3]), "+v"(swr[4]), "+v"(swr[5]),
-                      "+v"(swr[6]), "+v"(swr[7]));
-    if constexpr (STAGE == 2) {
-      // #1: every wave holds its W fragments and scales of stage t & 1
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    i32x8 b[8];
-    int sa[8], sw[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      b[n] = mx_join(bl[n], bh[n]);
-      sa[n] = (int)(sar[n] >> sh);
-      sw[n] = (int)(swr[n] >> sh);
-    }
-    unroll<8>([&](auto mc) {
-      constexpr int m = mc.value;
-      if constexpr (m > 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(al[m & 1]), "+v"(ah[m & 1])::"memory");
-      if constexpr (m < 7) {
-        mx_ds<(m + 1) * 2048>(al[(m + 1) & 1], a_lo + so);
-        mx_ds<(m + 1) * 2048>(ah[(m + 1) & 1], a_hi + so);
-      }
-      if constexpr (STAGE == 2 && (m == 3 || m == 7)) {
-        // #2, #3: every wave holds A rows 0-3 / 4-7 of its half (the read just issued at m = 3 is of row 4)
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const i32x8 a = mx_join(al[m & 1], ah[m & 1]);
-      unroll<8>([&](auto nc) {
-        constexpr int n = nc.value, P = mxk_piece_after<STAGE>(m * 8 + n);
-        mx_mma(acc[m][n], b[n], a, sw[n], sa[m]);
-        if constexpr (P >= 0) {
-          int go = more;
-          asm volatile("" : "+v"(go));
-          if (__builtin_amdgcn_readfirstlane(go)) dma(std::integral_constant<int, P>{}, kt);
-        }
-      });
-    });
+    mx_step<false>(
+        acc, frag, t & 1,
+        [&] {  // #1: every wave holds its W fragments and scales of stage t & 1
+          if constexpr (STAGE == 2) barrier();
+        },
+        [&](auto mc) {  // #2, #3: every wave holds A rows 0-3 / 4-7 of its half (the read just issued at m = 3 is of row 4)
+          if constexpr (STAGE == 2 && (mc.value == 3 || mc.value == 7)) barrier();
+        },
+        [&](auto sc) {
+          constexpr int P = mxk_piece_after<STAGE>(sc.value);
+          if constexpr (P >= 0) {
+            int go = more;
+            asm volatile("" : "+v"(go));
+            if (__builtin_amdgcn_readfirstlane(go)) dma(std::integral_constant<int, P>{}, kt);
+          }
+        });
     if (STAGE == 2 && more)
       asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    barrier();
   }
-
-  // the MFMAs are opaque to the compiler's hazard handling: let the last ones retire before their results are read
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  mxp_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
+  mx_drain();
+  mx_epilogue<EPI>(g, acc, m0, n0, wm, wn, fr, fc);
 }
 
-template <int EPI>
-int launch(const MxArgs& g, hipStream_t st) {
+// one launcher for the three kernels: the LDS attribute is set once per instantiation
+template <auto KERNEL>
+int mx_launch(const MxArgs& g, int grid, hipStream_t st) {
   static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
     return true;
   }();
   (void)attr;
-  const int nm = EPI == EPI_VT ? (g.M / g.rows_per_seg) * g.seg_mt : (g.M + BM - 1) / BM, nn = (g.N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm_mx_kernel<EPI>), dim3(nm * nn), dim3(256), LDS_TOTAL, st, g);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), LDS_TOTAL, st, g);
   SA_LAUNCH_CHECK();
   return SA_OK;
 }
@@ -819,21 +650,6 @@ int num_cus() {
   return cus[dev];
 }
 
-// workgroups: 0 = one per CU, > 0 = the cap on the grid (tests and A/B)
-template <int EPI>
-int launch_persistent(const MxArgs& g, int workgroups, hipStream_t st) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_mxp_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    return true;
-  }();
-  (void)attr;
-  const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-  const int grid = min(tiles, workgroups > 0 ? workgroups : num_cus());
-  hipLaunchKernelGGL((gemm_mxp_kernel<EPI>), dim3(grid), dim3(256), LDS_TOTAL, st, g);
-  SA_LAUNCH_CHECK();
-  return SA_OK;
-}
-
 enum { KSTEP_AUTO = 0, KSTEP_ONE_BARRIER = 1, KSTEP_SPLIT = 2 };
 // what auto resolves to for the one-tile kernels (DESIGN.md "MXFP8 GEMM K step", Decision; bit-identical either way):
 // the default step, and the split step from SA_MXGEMM_KSTEP_SPLIT_MIN_NK K-tiles on -- the measured win is the 70-step
@@ -860,27 +676,32 @@ int auto_kstep(int nk) {
   return nk >= SA_MXGEMM_KSTEP_SPLIT_MIN_NK ? KSTEP_SPLIT : SA_MXGEMM_KSTEP_DEFAULT;
 }
 
-template <int EPI>
-int launch_kstep(const MxArgs& g, hipStream_t st) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_mxk_kernel<EPI, SA_MXGEMM_KSTEP_STAGE>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    return true;
-  }();
-  (void)attr;
-  const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-  hipLaunchKernelGGL((gemm_mxk_kernel<EPI, SA_MXGEMM_KSTEP_STAGE>), dim3(tiles), dim3(256), LDS_TOTAL, st, g);
-  SA_LAUNCH_CHECK();
-  return SA_OK;
-}
-
-// auto, per launch: a persistent selection (explicit, or auto under SA_MXGEMM_KERNEL=2) keeps the one-barrier step
+// auto, per launch: a persistent selection (explicit, or auto under SA_MXGEMM_KERNEL=2) keeps the one-barrier step.
+// workgroups: 0 = one per CU, > 0 = the cap on the persistent grid (tests and A/B)
 template <int EPI>
 int launch_sel(const MxArgs& g, int kernel, int workgroups, int kstep, hipStream_t st) {
   if (kernel == KERNEL_AUTO && kstep != KSTEP_SPLIT) kernel = env_kernel();
   if (kstep == KSTEP_AUTO) kstep = kernel == KERNEL_PERSISTENT ? KSTEP_ONE_BARRIER : auto_kstep(g.K / BKB);
-  if (kstep == KSTEP_SPLIT) return launch_kstep<EPI>(g, st);
-  return kernel == KERNEL_PERSISTENT ? launch_persistent<EPI>(g, workgroups, st) : launch<EPI>(g, st);
+  if (kstep == KSTEP_SPLIT) return mx_launch<gemm_mxk_kernel<EPI, SA_MXGEMM_KSTEP_STAGE>>(g, mx_tiles(g), st);
+  if (kernel == KERNEL_PERSISTENT)
+    return mx_launch<gemm_mxp_kernel<EPI>>(g, min(mx_tiles(g), workgroups > 0 ? workgroups : num_cus()), st);
+  return mx_launch<gemm_mx_kernel<EPI>>(g, mx_tiles(g), st);
+}
+
+// what every GEMM entry point asks of its operands (out: C or vt_out)
+int check_operands(const void* A, int64_t lda, const void* SA, int64_t ldsa, const void* W, int64_t ldw, const void* SW,
+                   int64_t ldsw, const void* out, int M, int N, int K) {
+  if (!A || !SA || !W || !SW || !out || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
+  if (K % BKB != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldsa < K / 32 || ldsw < K / 32)
+    return SA_ERR_ARG;
+  if ((((uintptr_t)A) & 15) || (((uintptr_t)W) & 15)) return SA_ERR_ARG;
+  // a K-tile's four scale bytes of a row are fetched as one dword
+  if (ldsa % 4 != 0 || ldsw % 4 != 0 || (((uintptr_t)SA) & 3) || (((uintptr_t)SW) & 3)) return SA_ERR_ARG;
+  // 32-bit element / scale offsets inside the kernel
+  if ((long)M * lda >= 0x7fffffffL || (long)N * ldw >= 0x7fffffffL || (long)M * ldsa >= 0x7fffffffL ||
+      (long)N * ldsw >= 0x7fffffffL)
+    return SA_ERR_ARG;
+  return SA_OK;
 }
 
 struct QuantArgs {
@@ -933,16 +754,7 @@ extern "C" int sa_gemm_mxfp8_ks(const void* A, int64_t lda, const void* A_scales
   if (kstep < KSTEP_AUTO || kstep > KSTEP_SPLIT) return SA_ERR_ARG;
   // the new step is a one-tile kernel: no persistent form, no grid cap
   if (kstep == KSTEP_SPLIT && (kernel == KERNEL_PERSISTENT || workgroups != 0)) return SA_ERR_ARG;
-  if (!A || !A_scales || !W || !W_scales || !C || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
-  if (K % BKB != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 || ldws < K / 32)
-    return SA_ERR_ARG;
-  if ((((uintptr_t)A) & 15) || (((uintptr_t)W) & 15)) return SA_ERR_ARG;
-  // a K-tile's four scale bytes of a row are fetched as one dword
-  if (ldas % 4 != 0 || ldws % 4 != 0 || (((uintptr_t)A_scales) & 3) || (((uintptr_t)W_scales) & 3)) return SA_ERR_ARG;
-  // 32-bit element / scale offsets inside the kernel
-  if ((long)M * lda >= 0x7fffffffL || (long)N * ldw >= 0x7fffffffL || (long)M * ldas >= 0x7fffffffL ||
-      (long)N * ldws >= 0x7fffffffL)
-    return SA_ERR_ARG;
+  if (check_operands(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, C, M, N, K) != SA_OK) return SA_ERR_ARG;
   if (ldc < N || ldc % 4 != 0 || (((uintptr_t)C) & 15)) return SA_ERR_ARG;  // 4-column vector stores
   if (epilogue == EPI_RES_F32 &&
       (!residual || ldr % 4 != 0 || (((uintptr_t)residual) & 15) || (gate && rows_per_batch <= 0))) return SA_ERR_ARG;
@@ -985,21 +797,14 @@ extern "C" int sa_gemm_mxfp8_vt(const void* A, int64_t lda, const void* A_scales
                                 int64_t ldw, const void* W_scales, int64_t ldws, const float* bias, void* vt_out,
                                 void* vt_scales, int64_t Rv, int M, int N, int K, int rows_per_seg, int nseg,
                                 void* stream) {
-  if (!A || !A_scales || !W || !W_scales || !vt_out || !vt_scales || M <= 0 || N <= 0 || K <= 0) return SA_ERR_ARG;
+  if (check_operands(A, lda, A_scales, ldas, W, ldw, W_scales, ldws, vt_out, M, N, K) != SA_OK) return SA_ERR_ARG;
+  if (!vt_scales || N % 128 != 0) return SA_ERR_ARG;
   if (rows_per_seg <= 0 || nseg <= 0 || (long)nseg * rows_per_seg != M) return SA_ERR_ARG;
-  if (K % BKB != 0 || N % 128 != 0 || lda % 16 != 0 || ldw % 16 != 0 || lda < K || ldw < K || ldas < K / 32 ||
-      ldws < K / 32)
-    return SA_ERR_ARG;
-  if ((((uintptr_t)A) & 15) || (((uintptr_t)W) & 15)) return SA_ERR_ARG;
-  if (ldas % 4 != 0 || ldws % 4 != 0 || (((uintptr_t)A_scales) & 3) || (((uintptr_t)W_scales) & 3)) return SA_ERR_ARG;
-  if ((long)M * lda >= 0x7fffffffL || (long)N * ldw >= 0x7fffffffL || (long)M * ldas >= 0x7fffffffL ||
-      (long)N * ldws >= 0x7fffffffL)
-    return SA_ERR_ARG;
   // every segment owns ceil128(rows_per_seg) columns of the Rv; 16-byte stores into vt_out
   const long seg_cols = ((long)rows_per_seg + 127) / 128 * 128;
   if (Rv <= 0 || Rv % 128 != 0 || Rv < nseg * seg_cols || (((uintptr_t)vt_out) & 15)) return SA_ERR_ARG;
   MxArgs g{(const uint8_t*)A, lda, (const uint8_t*)A_scales, ldas, (const uint8_t*)W, ldw, (const uint8_t*)W_scales, ldws,
            bias, vt_out, Rv, (uint8_t*)vt_scales, Rv / 32, nullptr, 0, nullptr, 0, 1, M, N, K, 8, rows_per_seg,
            (rows_per_seg + BM - 1) / BM};
-  return launch<EPI_VT>(g, (hipStream_t)stream);
+  return mx_launch<gemm_mx_kernel<EPI_VT>>(g, mx_tiles(g, true), (hipStream_t)stream);
 }

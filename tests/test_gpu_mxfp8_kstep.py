@@ -3,9 +3,8 @@ byte: both add each accumulator's K-tiles in the same order with one MFMA per K-
 output byte and every scale byte must be equal.  The shapes are the smallest at which a two-deep, region-freed pipeline
 can go wrong -- no K-tile t + 1, no K-tile t + 2, the first step that ends on a counted vmcnt, both ring parities at the
 drain, clamped rows re-read by the early DMA, the raster's short last run, the DiT's 12- and 70-step tiles, more tiles
-than CUs.  The buffers carry guard rows and columns: a store past M or N shows as a changed guard.  The helpers are those
-of tests/test_gpu_mxfp8_persistent.py."""
-import functools
+than CUs.  The buffers carry guard rows and columns: a store past M or N shows as a changed guard.  The helpers are
+tests/mxgemm_util.py's."""
 import os
 import subprocess
 import sys
@@ -16,71 +15,18 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
-from stableavatar_amd import mxfp8, ops  # noqa: E402
+from mxgemm_util import ALL, BF16, DEV, EPI_ID, F32, GELU, GELU_MX, RES, guards_intact, launch, problem  # noqa: E402
+
+from stableavatar_amd import ops  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-BF16, GELU, F32, RES, GELU_MX = (ops.EPI_BF16, ops.EPI_GELU_TANH_BF16, ops.EPI_F32, ops.EPI_RES_F32,
-                                 ops.EPI_GELU_TANH_MXFP8)
-ALL = [BF16, GELU, F32, RES, GELU_MX]
-EPI_ID = {BF16: "bf16", GELU: "gelu", F32: "f32", RES: "res", GELU_MX: "gelu_mx"}
-GUARD_ROWS, GUARD_COLS = 8, 32
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(M, N, K):
-    """seeded bf16 data quantised by the definition: activations with per-row magnitudes 2^-3 .. 2^3, weights ~ 0.05,
-    a bias, a residual and one gate row per 100 rows (the widest use)"""
-    g = torch.Generator().manual_seed(1000 * M + 10 * N + K)
-    a = (torch.randn(M, K, generator=g) * torch.exp2(torch.randint(-3, 4, (M, 1), generator=g).float())).bfloat16()
-    w = (torch.randn(N, K, generator=g) * 0.05).bfloat16()
-    aq, as_ = mxfp8.quantize(a)
-    wq, ws = mxfp8.quantize(w)
-    return dict(a=ops.Mx8(aq.to(DEV), as_.to(DEV)), w=ops.Mx8(wq.to(DEV), ws.to(DEV)),
-                bias=(torch.randn(N, generator=g) * 0.5).to(DEV), res=torch.randn(M, N, generator=g).to(DEV),
-                gate=torch.randn(-(-M // 100) + 1, N, generator=g).to(DEV))
-
-
-def _launch(p, epi, kstep, rows_per_batch=100, in_place=False):
-    """one launch of the one-tile kernel under the given K step into guarded buffers; returns the whole buffers (output
-    bytes, and scale bytes for epilogue 8)"""
-    M, N = p["a"].shape[0], p["w"].shape[0]
-    if epi == GELU_MX:
-        q = torch.full((M + GUARD_ROWS, N + GUARD_COLS), 0xA5, dtype=torch.uint8, device=DEV)
-        s = torch.full((M + GUARD_ROWS, N // 32 + 4), 0xA5, dtype=torch.uint8, device=DEV)
-        ops.linear_mxfp8(p["a"], p["w"], p["bias"], epi, out=ops.Mx8(q[:M, :N], s[:M, :N // 32]), kernel=1, kstep=kstep)
-        bufs = (q, s)
-    else:
-        dt = torch.float32 if epi in (F32, RES) else torch.bfloat16
-        c = torch.full((M + GUARD_ROWS, N + GUARD_COLS), -7.0, dtype=dt, device=DEV)
-        kw = {}
-        if epi == RES:
-            res = p["res"]
-            if in_place:  # the residual aliases C, as the DiT's FFN-down runs
-                c[:M, :N] = res
-                res = c[:M, :N]
-            kw = dict(residual=res, gate=p["gate"], rows_per_batch=rows_per_batch)
-        ops.linear_mxfp8(p["a"], p["w"], p["bias"], epi, out=c[:M, :N], kernel=1, kstep=kstep, **kw)
-        bufs = (c,)
-    torch.cuda.synchronize()
-    return bufs
-
-
-def _guards_intact(bufs, M, N, epi):
-    c = bufs[0]
-    fill = 0xA5 if epi == GELU_MX else -7.0
-    ok = bool((c[M:] == fill).all() and (c[:, N:] == fill).all())
-    if epi == GELU_MX:
-        s = bufs[1]
-        ok = ok and bool((s[M:] == fill).all() and (s[:, N // 32:] == fill).all())
-    return ok
 
 
 def _check(M, N, K, epi, rows_per_batch=100, in_place=False):
-    p = _problem(M, N, K)
-    ref = _launch(p, epi, 1, rows_per_batch, in_place)
-    out = _launch(p, epi, 2, rows_per_batch, in_place)
-    assert _guards_intact(ref, M, N, epi) and _guards_intact(out, M, N, epi)
+    p = problem(M, N, K)
+    ref = launch(p, epi, 1, kstep=1, rows_per_batch=rows_per_batch, in_place=in_place)
+    out = launch(p, epi, 1, kstep=2, rows_per_batch=rows_per_batch, in_place=in_place)
+    assert guards_intact(ref, M, N, epi) and guards_intact(out, M, N, epi)
     for r, o in zip(ref, out):  # the output; the scales too for epilogue 8
         assert torch.equal(r, o), (M, N, K, epi, int((r != o).sum()))
     # the launch wrote: no live element still holds the fill
