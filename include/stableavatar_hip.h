@@ -271,6 +271,23 @@ int sa_attn_fwd_mxfp8_split(const void* q, const void* q_scales, const void* k, 
                             const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim,
                             const int32_t* o_rows, int split_tiles, void* work, int64_t work_bytes, void* stream);
 
+/* ---- fp8 self-O mode: the flash kernel hands the O-projection its MXFP8 operand (opt-in) ----
+ * sa_attn_fwd_mxfp8 / sa_attn_fwd_mxfp8_split with the bf16 output replaced by o_q (uint8 [rows][ldo] e4m3 bytes,
+ * ldo >= heads * 128) and o_scales (uint8 [rows][ldos] E8M0 bytes, ldos >= heads * 4; byte h * 4 + b scales columns
+ * 128 h + 32 b .. + 31): byte for byte the parent entry point writing bf16 followed by sa_mxfp8_quant of that output,
+ * for every row the parent writes (o_rows honoured alike; rows at or past q_len and columns past heads * 128 are not
+ * written).  A segment with kv_len == 0 writes zero bytes and scale byte 127.  The arguments are checked as the
+ * parent's, and ldo % 4 == 0, ldos % 4 == 0, o_q and o_scales 4-B aligned (dword stores), before the first HIP call. */
+int sa_attn_fwd_mxfp8_o8(const void* q, const void* q_scales, const void* k, const void* k_scales, const void* vt,
+                         const void* vt_scales, int64_t Rv, void* o_q, int64_t ldo, void* o_scales, int64_t ldos,
+                         const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len, int heads, int head_dim,
+                         const int32_t* o_rows, void* stream);
+int sa_attn_fwd_mxfp8_split_o8(const void* q, const void* q_scales, const void* k, const void* k_scales,
+                               const void* vt, const void* vt_scales, int64_t Rv, void* o_q, int64_t ldo,
+                               void* o_scales, int64_t ldos, const int32_t* segs, const int32_t* vcol0, int nseg,
+                               int max_q_len, int heads, int head_dim, const int32_t* o_rows, int split_tiles,
+                               void* work, int64_t work_bytes, void* stream);
+
 /* ---- fp8 q/k/v mode feeding the fp8 attention directly (opt-in; no counterpart in the reference) ----
  * Three entry points that write the operands of sa_attn_fwd_mxfp8 where their values are made.  Each is bit-identical
  * to the pair of calls it replaces, and checks every argument before its first HIP call. */

@@ -33,6 +33,8 @@ SIGNATURES = {
     "sa_attn_pack_mxfp8": "plplplppiiiiifppppppplp",
     "sa_attn_fwd_mxfp8": "pppppplplppiiiipp",
     "sa_attn_fwd_mxfp8_split": "pppppplplppiiiipiplp",
+    "sa_attn_fwd_mxfp8_o8": "pppppplplplppiiiipp",
+    "sa_attn_fwd_mxfp8_split_o8": "pppppplplplppiiiipiplp",
     "sa_gemm_mxfp8_vt": "plplplplpppliiiiip",
     "sa_qk_rmsnorm_rope_mxfp8": "pliippiiifpiiiiiiiplplfp",
     "sa_attn_pack_k_mxfp8": "plpiiipppp",

@@ -31,6 +31,19 @@
 // attn_mx_split_merge_kernel: o = (w0 O0 + w1 O1) / (w0 l0 + w1 l1), w_h = exp2(m_h - max(m0, m1)), and w_h = 0
 // for a half whose reported maximum stands more than FLUSH_GAP below the other's: its true maximum then stands
 // more than 10 + P_SHIFT below the row's, the definition's drop rule (mxfp8_attn.attend_split).  No keys at all: zeros.
+//
+// sa_attn_fwd_mxfp8_o8 / sa_attn_fwd_mxfp8_split_o8 (the fp8 self-O mode): the same kernels with O8 set, a switch on
+// the epilogue alone.  The output leaves as the MXFP8 operand of the O-projection -- the bf16-rounded O quantised
+// along the row, bit for bit the bf16 entry point followed by sa_mxfp8_quant -- as bytes o_q [rows][ldo] and scale
+// bytes o_scales [rows][ldos], byte 4 h + b for columns 128 h + 32 b .. of head h.  In the flash kernel lane
+// (query r16, group g) holds O[dt][qt][e] = column 16 dt + 4 g + e, so block b of a query is d tiles 2 b and 2 b + 1
+// over the four lanes r16 + 16 g, eight values a lane: round to bf16, the lane's amax, shfl_xor 16 and 32 for the
+// block's, mx_quant8 (mxfp8.h's rule), one dword store per d tile at column 16 dt + 4 g; the lane with g = 0 writes
+// the head's four scale bytes as one dword.  In the merge a thread holds four columns of a row, a block is eight
+// adjacent threads (shfl_xor 1, 2, 4), and the block's first thread writes its scale byte.  Lanes that share a block
+// share the query, so they skip rows at or past q_len together.  kv_len == 0: zero bytes, scale byte 127.
+#include <type_traits>
+
 #include "mxfp8.h"
 
 namespace {
@@ -61,6 +74,13 @@ struct FwdArgs {
   const int* segs; const int* vcol0; const int* orows;
   int heads;
 };
+// O8: o / os are the operand's bytes and their row stride in bytes; sc / lds the scale bytes and their row stride.
+// (A type of its own for the O8 instantiations, so the kernel arguments of the others stay where they were.)
+struct FwdArgs8 : FwdArgs {
+  uint8_t* sc; long lds;
+};
+template <bool O8>
+using FwdArgsOf = std::conditional_t<O8, FwdArgs8, FwdArgs>;
 // the key-split launch (the header comment): tile decode and the partials
 struct SplitArgs {
   int nqb, split_full;  // query blocks per (segment, head); the number of whole tiles
@@ -104,8 +124,8 @@ __device__ __forceinline__ void read4(u32x4 (&lo)[4], u32x4 (&hi)[4], uint32_t (
 
 // (a template on the kernel itself: called as an inlined body from two wrappers, as attention.hip's split is, the
 // compiler schedules the unsplit instantiation differently; this way its instruction stream is what it was)
-template <bool SPLIT>
-__global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a, SplitArgs sp) {
+template <bool SPLIT, bool O8>
+__global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgsOf<O8> a, SplitArgs sp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int qb, h, seg, half = -1, stile = 0;
   if constexpr (SPLIT) {
@@ -156,6 +176,17 @@ __global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a, SplitArgs s
   }
   const int nkb = (kv_len + KVB - 1) / KVB;
   if (kv_len <= 0) {
+    if constexpr (O8) {  // all-zero blocks: zero bytes (dword stores, as the epilogue's), scale byte 127
+      for (int i = tid; i < QBW * (D / 4); i += 512) {
+        const int qi = qb * QBW + i / (D / 4);
+        if (qi < q_len) {
+          const long orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
+          *(uint32_t*)((uint8_t*)a.o + orow * a.os + h * D + (i % (D / 4)) * 4) = 0u;
+          if (i % (D / 4) == 0) *(uint32_t*)(a.sc + orow * a.lds + h * 4) = 0x7f7f7f7fu;
+        }
+      }
+      return;
+    }
     for (int i = tid; i < QBW * (D / 8); i += 512) {
       const int qi = qb * QBW + i / (D / 8);
       if (qi < q_len) {
@@ -353,18 +384,39 @@ __global__ __launch_bounds__(512) void attn_fwd_mx_kernel(FwdArgs a, SplitArgs s
     const float inv = 1.0f / L[qt][0];
     const int qrow = q_row0 + qi;
     const int orow = a.orows ? a.orows[qrow] : qrow;
-    bf16* op = a.o + (long)orow * a.os + h * D + 4 * g;
+    if constexpr (O8) {  // the header comment: the four lanes r16 + 16 g of a query all get here or none does
+      uint8_t* op = (uint8_t*)a.o + (long)orow * a.os + h * D + 4 * g;
+      uint32_t sc4 = 0;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      const f32x4& v = O[dt][qt];
-      *(bf16x4*)(op + dt * 16) = (bf16x4){f2bf(v[0] * inv), f2bf(v[1] * inv), f2bf(v[2] * inv), f2bf(v[3] * inv)};
+      for (int b = 0; b < 4; ++b) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(O[2 * b + (j >> 2)][qt][j & 3] * inv));
+        float amax = mx_amax8(v);
+        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+        uint32_t s;
+        const u32x2 w = mx_quant8(v, amax, &s);
+        *(uint32_t*)(op + 32 * b) = w[0];
+        *(uint32_t*)(op + 32 * b + 16) = w[1];
+        sc4 |= s << (8 * b);
+      }
+      if (g == 0) *(uint32_t*)(a.sc + (long)orow * a.lds + h * 4) = sc4;
+    } else {
+      bf16* op = a.o + (long)orow * a.os + h * D + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) {
+        const f32x4& v = O[dt][qt];
+        *(bf16x4*)(op + dt * 16) = (bf16x4){f2bf(v[0] * inv), f2bf(v[1] * inv), f2bf(v[2] * inv), f2bf(v[3] * inv)};
+      }
     }
   }
 }
 
 // the two key halves of each split tile -> the output (the header comment).  A thread takes four d of a row: 32
 // threads a row, so a wave reads 128 contiguous bytes of each half's d tile and writes two 256-byte rows
-__global__ __launch_bounds__(256) void attn_mx_split_merge_kernel(FwdArgs a, SplitArgs sp) {
+template <bool O8>
+__global__ __launch_bounds__(256) void attn_mx_split_merge_kernel(FwdArgsOf<O8> a, SplitArgs sp) {
   const int stile = blockIdx.x, tile = sp.split_full + stile;
   const int qb = tile % sp.nqb, h = (tile / sp.nqb) % a.heads, seg = tile / (sp.nqb * a.heads);
   const int* sg = a.segs + seg * 4;
@@ -376,7 +428,7 @@ __global__ __launch_bounds__(256) void attn_mx_split_merge_kernel(FwdArgs a, Spl
   const float* w1 = w0 + WBLK;
   for (int i = threadIdx.x; i < QBW * (D / 4); i += 256) {
     const int row = i / (D / 4), c = i % (D / 4), qi = qb * QBW + row;
-    if (qi >= q_len) continue;
+    if (qi >= q_len) continue;  // a row is 32 threads: the eight threads of an O8 block skip together
     u32x2 out = {0u, 0u};
     if (kv_len > 0) {
       const float m0 = w0[QBW * D + row], m1 = w1[QBW * D + row];
@@ -391,7 +443,20 @@ __global__ __launch_bounds__(256) void attn_mx_split_merge_kernel(FwdArgs a, Spl
       out = __builtin_bit_cast(u32x2, o4);
     }
     const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
-    *(u32x2*)(a.o + (long)orow * a.os + h * D + 4 * c) = out;
+    if constexpr (O8) {  // the bf16 values quantised; no key at all: zeros, an all-zero block (scale byte 127)
+      const bf16x4 o4 = __builtin_bit_cast(bf16x4, out);
+      const float v0 = bf2f(o4[0]), v1 = bf2f(o4[1]), v2 = bf2f(o4[2]), v3 = bf2f(o4[3]);
+      float amax = fmaxf(fmaxf(fabsf(v0), fabsf(v1)), fmaxf(fabsf(v2), fabsf(v3)));
+      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+      const uint32_t s = mx_scale_byte(amax);
+      const float k = mx_inv_scale(s);
+      *(uint32_t*)((uint8_t*)a.o + (long)orow * a.os + h * D + 4 * c) = mx_pack4(v0 * k, v1 * k, v2 * k, v3 * k);
+      if ((c & 7) == 0) a.sc[(long)orow * a.lds + h * 4 + (c >> 3)] = (uint8_t)s;
+    } else {
+      *(u32x2*)(a.o + (long)orow * a.os + h * D + 4 * c) = out;
+    }
   }
 }
 
@@ -603,29 +668,73 @@ extern "C" int sa_attn_pack_k_mxfp8(const void* k, int64_t k_stride, const int32
   return SA_OK;
 }
 
-extern "C" int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void* k, const void* k_scales,
-                                 const void* vt, const void* vt_scales, int64_t Rv, void* o, int64_t o_stride,
-                                 const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len, int heads,
-                                 int head_dim, const int32_t* o_rows, void* stream) {
-  if (!q || !q_scales || !k || !k_scales || !vt || !vt_scales || !o || !segs || !vcol0) return SA_ERR_ARG;
-  if (nseg <= 0 || heads <= 0 || head_dim != D || max_q_len <= 0) return SA_ERR_ARG;
-  if (Rv <= 0 || Rv % KVB) return SA_ERR_ARG;
-  if (o_stride < (int64_t)heads * D || o_stride % 8 || (((uintptr_t)o) & 15)) return SA_ERR_ARG;
-  // 16-byte operand loads, dword scale loads
-  if ((((uintptr_t)q) & 15) || (((uintptr_t)k) & 15) || (((uintptr_t)vt) & 15)) return SA_ERR_ARG;
-  if ((((uintptr_t)q_scales) & 3) || (((uintptr_t)k_scales) & 3) || (((uintptr_t)vt_scales) & 3)) return SA_ERR_ARG;
+// the argument checks the four flash entry points share (16-byte operand loads, dword scale loads)
+static bool fwd_operands_ok(const void* q, const void* q_scales, const void* k, const void* k_scales, const void* vt,
+                            const void* vt_scales, int64_t Rv, const int32_t* segs, const int32_t* vcol0, int nseg,
+                            int max_q_len, int heads, int head_dim) {
+  if (!q || !q_scales || !k || !k_scales || !vt || !vt_scales || !segs || !vcol0) return false;
+  if (nseg <= 0 || heads <= 0 || head_dim != D || max_q_len <= 0) return false;
+  if (Rv <= 0 || Rv % KVB) return false;
+  if ((((uintptr_t)q) & 15) || (((uintptr_t)k) & 15) || (((uintptr_t)vt) & 15)) return false;
+  if ((((uintptr_t)q_scales) & 3) || (((uintptr_t)k_scales) & 3) || (((uintptr_t)vt_scales) & 3)) return false;
+  return true;
+}
+// the bf16 output: 8- and 16-byte stores
+static bool fwd_out_ok(const void* o, int64_t o_stride, int heads) {
+  return o && o_stride >= (int64_t)heads * D && o_stride % 8 == 0 && !(((uintptr_t)o) & 15);
+}
+// the MXFP8 output: dword stores of bytes and of a head's four scale bytes
+static bool fwd_out8_ok(const void* o_q, int64_t ldo, const void* o_scales, int64_t ldos, int heads) {
+  if (!o_q || !o_scales || ldo < (int64_t)heads * D || ldos < (int64_t)heads * 4 || ldo % 4 || ldos % 4) return false;
+  return !(((uintptr_t)o_q) & 3) && !(((uintptr_t)o_scales) & 3);
+}
+
+template <bool O8>
+static int fwd_launch(const FwdArgsOf<O8>& a, int nseg, int max_q_len, void* stream) {
   static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<false, O8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               LDS_TOTAL);
     return true;
   }();
   (void)attr;
-  FwdArgs a{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
-            (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o, o_stride, segs, vcol0, o_rows, heads};
-  hipLaunchKernelGGL(attn_fwd_mx_kernel<false>, dim3((max_q_len + QBW - 1) / QBW, heads, nseg), dim3(512), LDS_TOTAL,
-                     (hipStream_t)stream, a, SplitArgs{});
+  hipLaunchKernelGGL((attn_fwd_mx_kernel<false, O8>), dim3((max_q_len + QBW - 1) / QBW, a.heads, nseg), dim3(512),
+                     LDS_TOTAL, (hipStream_t)stream, a, SplitArgs{});
   SA_LAUNCH_CHECK();
   return SA_OK;
+}
+
+template <bool O8>
+static int fwd_split_launch(const FwdArgsOf<O8>& a, int nseg, int max_q_len, int split_tiles, void* work,
+                            int64_t work_bytes, void* stream) {
+  const int nqb = (max_q_len + QBW - 1) / QBW;
+  const int64_t ntiles = (int64_t)nseg * a.heads * nqb;
+  if (!work || split_tiles <= 0 || split_tiles > ntiles || ntiles + split_tiles > 0x7fffffff) return SA_ERR_ARG;
+  if ((((uintptr_t)work) & 15) || work_bytes < (int64_t)split_tiles * 2 * WBLK * 4) return SA_ERR_ARG;
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<true, O8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_TOTAL);
+    return true;
+  }();
+  (void)attr;
+  SplitArgs sp{nqb, (int)(ntiles - split_tiles), (float*)work};
+  hipLaunchKernelGGL((attn_fwd_mx_kernel<true, O8>), dim3((unsigned)(ntiles + split_tiles)), dim3(512), LDS_TOTAL,
+                     (hipStream_t)stream, a, sp);
+  SA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_mx_split_merge_kernel<O8>, dim3(split_tiles), dim3(256), 0, (hipStream_t)stream, a, sp);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+extern "C" int sa_attn_fwd_mxfp8(const void* q, const void* q_scales, const void* k, const void* k_scales,
+                                 const void* vt, const void* vt_scales, int64_t Rv, void* o, int64_t o_stride,
+                                 const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len, int heads,
+                                 int head_dim, const int32_t* o_rows, void* stream) {
+  if (!fwd_operands_ok(q, q_scales, k, k_scales, vt, vt_scales, Rv, segs, vcol0, nseg, max_q_len, heads, head_dim) ||
+      !fwd_out_ok(o, o_stride, heads))
+    return SA_ERR_ARG;
+  FwdArgs a{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
+            (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o, o_stride, segs, vcol0, o_rows, heads};
+  return fwd_launch<false>(a, nseg, max_q_len, stream);
 }
 
 extern "C" int sa_attn_fwd_mxfp8_split(const void* q, const void* q_scales, const void* k, const void* k_scales,
@@ -633,29 +742,37 @@ extern "C" int sa_attn_fwd_mxfp8_split(const void* q, const void* q_scales, cons
                                        const int32_t* segs, const int32_t* vcol0, int nseg, int max_q_len, int heads,
                                        int head_dim, const int32_t* o_rows, int split_tiles, void* work,
                                        int64_t work_bytes, void* stream) {
-  if (!q || !q_scales || !k || !k_scales || !vt || !vt_scales || !o || !segs || !vcol0 || !work) return SA_ERR_ARG;
-  if (nseg <= 0 || heads <= 0 || head_dim != D || max_q_len <= 0) return SA_ERR_ARG;
-  if (Rv <= 0 || Rv % KVB) return SA_ERR_ARG;
-  if (o_stride < (int64_t)heads * D || o_stride % 8 || (((uintptr_t)o) & 15)) return SA_ERR_ARG;
-  if ((((uintptr_t)q) & 15) || (((uintptr_t)k) & 15) || (((uintptr_t)vt) & 15)) return SA_ERR_ARG;
-  if ((((uintptr_t)q_scales) & 3) || (((uintptr_t)k_scales) & 3) || (((uintptr_t)vt_scales) & 3)) return SA_ERR_ARG;
-  const int nqb = (max_q_len + QBW - 1) / QBW;
-  const int64_t ntiles = (int64_t)nseg * heads * nqb;
-  if (split_tiles <= 0 || split_tiles > ntiles || ntiles + split_tiles > 0x7fffffff) return SA_ERR_ARG;
-  if ((((uintptr_t)work) & 15) || work_bytes < (int64_t)split_tiles * 2 * WBLK * 4) return SA_ERR_ARG;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_mx_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_TOTAL);
-    return true;
-  }();
-  (void)attr;
+  if (!fwd_operands_ok(q, q_scales, k, k_scales, vt, vt_scales, Rv, segs, vcol0, nseg, max_q_len, heads, head_dim) ||
+      !fwd_out_ok(o, o_stride, heads))
+    return SA_ERR_ARG;
   FwdArgs a{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
             (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o, o_stride, segs, vcol0, o_rows, heads};
-  SplitArgs sp{nqb, (int)(ntiles - split_tiles), (float*)work};
-  hipLaunchKernelGGL(attn_fwd_mx_kernel<true>, dim3((unsigned)(ntiles + split_tiles)), dim3(512), LDS_TOTAL,
-                     (hipStream_t)stream, a, sp);
-  SA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attn_mx_split_merge_kernel, dim3(split_tiles), dim3(256), 0, (hipStream_t)stream, a, sp);
-  SA_LAUNCH_CHECK();
-  return SA_OK;
+  return fwd_split_launch<false>(a, nseg, max_q_len, split_tiles, work, work_bytes, stream);
+}
+
+extern "C" int sa_attn_fwd_mxfp8_o8(const void* q, const void* q_scales, const void* k, const void* k_scales,
+                                    const void* vt, const void* vt_scales, int64_t Rv, void* o_q, int64_t ldo,
+                                    void* o_scales, int64_t ldos, const int32_t* segs, const int32_t* vcol0, int nseg,
+                                    int max_q_len, int heads, int head_dim, const int32_t* o_rows, void* stream) {
+  if (!fwd_operands_ok(q, q_scales, k, k_scales, vt, vt_scales, Rv, segs, vcol0, nseg, max_q_len, heads, head_dim) ||
+      !fwd_out8_ok(o_q, ldo, o_scales, ldos, heads))
+    return SA_ERR_ARG;
+  FwdArgs8 a{{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
+              (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o_q, ldo, segs, vcol0, o_rows, heads},
+             (uint8_t*)o_scales, ldos};
+  return fwd_launch<true>(a, nseg, max_q_len, stream);
+}
+
+extern "C" int sa_attn_fwd_mxfp8_split_o8(const void* q, const void* q_scales, const void* k, const void* k_scales,
+                                          const void* vt, const void* vt_scales, int64_t Rv, void* o_q, int64_t ldo,
+                                          void* o_scales, int64_t ldos, const int32_t* segs, const int32_t* vcol0,
+                                          int nseg, int max_q_len, int heads, int head_dim, const int32_t* o_rows,
+                                          int split_tiles, void* work, int64_t work_bytes, void* stream) {
+  if (!fwd_operands_ok(q, q_scales, k, k_scales, vt, vt_scales, Rv, segs, vcol0, nseg, max_q_len, heads, head_dim) ||
+      !fwd_out8_ok(o_q, ldo, o_scales, ldos, heads))
+    return SA_ERR_ARG;
+  FwdArgs8 a{{(const uint8_t*)q, (const uint8_t*)q_scales, (const uint8_t*)k, (const uint8_t*)k_scales,
+              (const uint8_t*)vt, (const uint8_t*)vt_scales, Rv, (bf16*)o_q, ldo, segs, vcol0, o_rows, heads},
+             (uint8_t*)o_scales, ldos};
+  return fwd_split_launch<true>(a, nseg, max_q_len, split_tiles, work, work_bytes, stream);
 }

@@ -24,6 +24,9 @@ Flag mapping:
 * ``--fp8_qkv`` (no counterpart in the reference): ``transformer.enable_fp8_qkv()``, the q/k/v Linears of the DiT
   blocks' self-attention on MXFP8 operands (DESIGN.md "fp8 q/k/v"); with ``--fp8_attn`` the attention operands are
   written by the V GEMM and the RoPE kernel themselves; changes numerics; combines with every flag above;
+* ``--fp8_o`` (no counterpart in the reference): ``transformer.enable_fp8_o()``, the output projection of the DiT
+  blocks' self-attention on MXFP8 operands (DESIGN.md "fp8 self-O"); with ``--fp8_attn`` the flash kernel writes the
+  projection's operand itself; changes numerics; combines with every flag above;
 * ``--fsdp_dit`` / ``--t5_fsdp`` / ``--t5_cpu`` / ``--offload_model``: accepted, no effect (the 3.5 GB DiT is
   replicated).
 Audio is read with scipy (16-bit / float WAV, channels averaged, polyphase resampling to 16 kHz) where the
@@ -106,6 +109,14 @@ def parse_args(argv=None):
                         "Measured: the chain from the LayerNorm to the attention's operands 1.25x, the 30-layer "
                         "forward with --fp8_attn --fp8_ffn 1.027x over those two alone, 1.28x over bf16 (DESIGN.md, "
                         "fp8 q/k/v).")
+    p.add_argument("--fp8_o", action="store_true",
+                   help="run the output projection of the DiT blocks' self-attention on MXFP8 operands (the bf16 "
+                        "attention output and the bf16 weight quantised, fp32 accumulation, the fp32 gated-residual "
+                        "epilogue unchanged; WanTransformer3DFantasyModel.enable_fp8_o). Changes numerics (about "
+                        "0.4e-2 rel-L2 per forward on top of bf16 on synthetic weights; real checkpoints unmeasured) "
+                        "and has no counterpart in the reference. With --fp8_attn the flash kernel writes the "
+                        "projection's MXFP8 operand itself; without it the bf16 output takes one more quantiser pass "
+                        "(DESIGN.md, fp8 self-O).")
     p.add_argument("--window_parallel", action="store_true",
                    help="multi-GPU: spread the sliding windows of each step over the ranks instead of sequence "
                         "parallelism (long clips, SURVEY.md §8(e))")
@@ -280,6 +291,10 @@ def main(argv=None):
         print("fp8 q/k/v: the DiT blocks' self-attention q/k/v Linears run on MXFP8 operands (numerics differ from "
               "the bf16 path)")
         transformer3d.enable_fp8_qkv()
+    if args.fp8_o:
+        print("fp8 self-O: the DiT blocks' self-attention output projection runs on MXFP8 operands (numerics differ "
+              "from the bf16 path)")
+        transformer3d.enable_fp8_o()
     if args.enable_teacache:
         coefficients = get_teacache_coefficients(root)
         if coefficients is not None:

@@ -5,6 +5,8 @@ against the bf16 kernels, ditfp8 = the whole forward with the mode off and on; a
 launch, bf16 against the fp8 attention mode's three kernels, ditfp8attn = the whole forward with that mode off, on, and
 on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (LayerNorm .. operands ready) in bf16, with the
 fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused;
+ofp8 = the MXFP8 flash kernel + the self-attention O-projection in bf16 and with the fp8 self-O mode unfused and fused,
+ditfp8o = the whole forward off / the three modes / the three + fp8 self-O unfused / fused;
 attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16.
 gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ks's one-tile kernel (the baseline arm) against its persistent kernel and
 against the one-tile kernel with the split K step (kstep=2) on their GEMM shapes, and ditfp8qkv has
@@ -291,6 +293,11 @@ def main(which=("gemm", "attn")):
     if "qkvfp8" in which:  # the fp8 q/k/v mode's operand chains against the bf16 one, interleaved rounds
         res.extend(bench_fp8_qkv())
         res.extend(bench_mxgemm_kernels(MXGEMM_QKV_SHAPES))
+    if "ofp8" in which:  # flash kernel + self-attention O-projection: bf16 against the fp8 self-O mode, interleaved
+        res.extend(bench_fp8_o())
+    if "ditfp8o" in which:  # whole-forward A/B of enable_fp8_o() on top of the other three modes, interleaved
+        res.append(bench_dit(fp8_o_ab=True))
+        print(json.dumps(res[-1]), flush=True)
     if "ditfp8qkv" in which:  # whole-forward A/B of enable_fp8_qkv() on top of the other two modes, interleaved
         res.append(bench_dit(fp8_qkv_ab=True))
         print(json.dumps(res[-1]), flush=True)
@@ -505,6 +512,89 @@ def bench_fp8_qkv(L=21504, H=12, B=3):
     return [r, r2]
 
 
+def bench_fp8_o(L=21504, H=12, B=3):
+    """The end of the self-attention half of a config-2 block (M = 3 x 21 504 rows, dim 1536, 12 heads; fp8 attention
+    on in all three arms), same process, interleaved rounds, median of 3: the MXFP8 flash kernel writing bf16 + the bf16
+    O-projection with its fp32 gated-residual epilogue (bf16: what the three existing modes run), the fp8 self-O mode
+    unfused (the same flash launch, the quantiser, the MXFP8 GEMM) and fused (the flash kernel writing the GEMM's
+    operand, the MXFP8 GEMM).  One JSON line for the chains, each timed as one sequence (ratio = bf16 ms / chain ms;
+    whether the fused operand equals the unfused one byte for byte), and one with every stage timed alone in the same
+    rounds, the MXFP8 O-projection also on the persistent kernel and on the split K step, and both projections in
+    place (output = residual, as the forward calls them)."""
+    dev, D = "cuda", 128
+    C, M = H * D, B * L
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(M, 3 * C, device=dev, generator=g).bfloat16()
+    x = torch.randn(M, C, device=dev, generator=g)
+    xo, xi = torch.empty_like(x), x.clone()
+    gate = torch.randn(B, C, device=dev, generator=g) * 0.3
+    w = (torch.randn(C, C, device=dev, generator=g) / C ** 0.5).bfloat16()
+    bias = torch.randn(C, device=dev, generator=g) * 0.1
+    w8 = ops.mxfp8_quant(w)
+    o = torch.empty(M, C, device=dev, dtype=torch.bfloat16)
+    oq, oq_f = ops.Mx8.empty(M, C, dev), ops.Mx8.empty(M, C, dev)
+    rows = [[b * L, L, b * L, L] for b in range(B)]
+    segs = torch.tensor(rows, dtype=torch.int32, device=dev)
+    vcol0, Rv = ops.attn_vcol0(rows)
+    vc = torch.tensor(vcol0, dtype=torch.int32, device=dev)
+    buf = ops.AttnMx8(M, M, H, Rv, B, dev)
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    ops.attn_pack_mxfp8(q, k, v, segs, vc, B, L, L, H, buf, kmean=ops.attn_kmean(k, segs, B, H, buf.kmean,
+                                                                                buf.kmean_work))
+    epi = dict(out=xo, residual=x, gate=gate, rows_per_batch=L)
+    inplace = dict(out=xi, residual=xi, gate=gate, rows_per_batch=L)  # as the forward calls it: x += gate * y
+    st = {
+        "flash_bf16": lambda: ops.attn_fwd_mxfp8(buf, o, segs, vc, B, L, H),
+        "flash_o8": lambda: ops.attn_fwd_mxfp8(buf, oq_f, segs, vc, B, L, H),
+        "quant": lambda: ops.mxfp8_quant(o, out=oq),
+        "oproj_bf16": lambda: ops.linear(o, w, bias, ops.EPI_RES_F32, **epi),
+        "oproj_mxfp8": lambda: ops.linear_mxfp8(oq, w8, bias, ops.EPI_RES_F32, **epi),
+        "oproj_mxfp8_f": lambda: ops.linear_mxfp8(oq_f, w8, bias, ops.EPI_RES_F32, **epi),
+        # the same GEMM on the MXFP8 GEMM's other kernels (auto is the one-tile kernel, one-barrier K step, at K = 1536)
+        "oproj_mxfp8_persistent": lambda: ops.linear_mxfp8(oq, w8, bias, ops.EPI_RES_F32, kernel=2, **epi),
+        "oproj_mxfp8_kstep2": lambda: ops.linear_mxfp8(oq, w8, bias, ops.EPI_RES_F32, kstep=2, **epi),
+        "oproj_bf16_inplace": lambda: ops.linear(o, w, bias, ops.EPI_RES_F32, **inplace),
+        "oproj_mxfp8_inplace": lambda: ops.linear_mxfp8(oq, w8, bias, ops.EPI_RES_F32, **inplace),
+    }
+    seq = {"bf16": ("flash_bf16", "oproj_bf16"), "unfused": ("flash_bf16", "quant", "oproj_mxfp8"),
+           "fused": ("flash_o8", "oproj_mxfp8_f")}
+
+    def chain(name):
+        def run():
+            for s_ in seq[name]:
+                st[s_]()
+        return run
+
+    fns = {n: chain(n) for n in seq}
+    fns.update(st)
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(3):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=10, warmup=1))
+        clocks.append(_sclk_mhz())
+    ms = {n: sorted(t)[1] for n, t in times.items()}
+    fns["bf16"]()
+    ref = xo.clone()
+    fns["unfused"]()
+    un = xo.clone()
+    fns["fused"]()
+    torch.cuda.synchronize()
+    same = torch.equal(oq.q, oq_f.q) and torch.equal(oq.s, oq_f.s) and torch.equal(un, xo)
+    r = {"kernel": "fp8o_chain", "M": M, "dim": C, "heads": H, "sclk_mhz": clocks, "fused_equals_unfused": same,
+         "rel_l2_fp8_o_vs_bf16_o": round(((xo - ref).norm() / ref.norm()).item(), 6)}
+    for n in seq:
+        r[f"{n}_ms"] = round(ms[n], 4)
+        r[f"{n}_rounds_ms"] = [round(t, 4) for t in times[n]]
+    r.update(ratio_unfused=round(ms["bf16"] / ms["unfused"], 4), ratio_fused=round(ms["bf16"] / ms["fused"], 4),
+             fused_vs_unfused=round(ms["unfused"] / ms["fused"], 4))
+    print(json.dumps(r), flush=True)
+    r2 = {"kernel": "fp8o_stages", "M": M}
+    r2.update({f"{n}_ms": round(ms[n], 4) for n in st})
+    r2.update({f"{n}_rounds_ms": [round(t, 4) for t in times[n]] for n in st})
+    print(json.dumps(r2), flush=True)
+    return [r, r2]
+
+
 # (name, M, N, K, epilogue): config 2 (M = 3 x 21 504) and the Ulysses N = 8 rank (M = 3 x 2 688) FFN, config-2 q|k, qkv
 MXGEMM_FFN_SHAPES = (("ffn_up", 64512, 8960, 1536, ops.EPI_GELU_TANH_MXFP8), ("ffn_down", 64512, 1536, 8960, ops.EPI_RES_F32),
                      ("ffn_up_rank8", 8064, 8960, 1536, ops.EPI_GELU_TANH_MXFP8),
@@ -709,7 +799,7 @@ def attn_clip_inputs(layers=(0, 15, 29)):
 
 
 def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False, fp8_attn_ab=False,
-              fp8_qkv_ab=False):
+              fp8_qkv_ab=False, fp8_o_ab=False):
     """One full 30-layer DiT forward at config 2 (B=3 CFG, 21 latent frames at 64x64, L=21504).
     attn_variants: time the forward under each self-attention schedule, interleaved rounds.
     fp8_ab: the forward with enable_fp8_ffn() off and on (two models on the same weights), interleaved rounds,
@@ -718,7 +808,8 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
     after each round.  fp8_qkv_ab: four variants on the same weights -- off; attention + FFN; those + enable_fp8_qkv()
     unfused; fused; fused with the MXFP8 GEMMs on their persistent kernel; and fused with every MXFP8 GEMM on the
     one-barrier K step -- each output's rel-L2 against off, whether fused equals unfused, and persistent and the
-    one-barrier step equal fused, byte for byte."""
+    one-barrier step equal fused, byte for byte.  fp8_o_ab: off; the three modes (attention + FFN + q/k/v); those +
+    enable_fp8_o() unfused; fused -- every round kept, each output's rel-L2 against off, whether fused equals unfused."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -829,6 +920,35 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
         for k in ("attn_ffn_qkv_unfused", "attn_ffn_qkv_fused", pers, ks1):
             r[f"ratio_{k}_vs_attn_ffn"] = round(r["attn_ffn_ms"] / r[f"{k}_ms"], 4)
         r["ratio_kstep_auto_vs_kstep1"] = round(r[f"{ks1}_ms"] / r["attn_ffn_qkv_fused_ms"], 4)
+        return r
+    if fp8_o_ab:
+        modes = {"off": m}
+        for k in ("three", "four_unfused", "four_fused"):
+            mm = WanTransformer3DFantasyModel(**cfg)
+            mm.load_state_dict(m.state_dict())
+            modes[k] = mm.to(dev)
+            modes[k].enable_fp8_attention(), modes[k].enable_fp8_ffn(), modes[k].enable_fp8_qkv()
+            if k != "three":
+                modes[k].enable_fp8_o()
+                modes[k]._fp8_o_fused = k.endswith("_fused")
+        times, clocks, outs = {k: [] for k in modes}, [], {}
+        with torch.no_grad():
+            for _ in range(3):
+                for k, mm in modes.items():
+                    f = lambda mm=mm: mm.forward_window(lat, 0, True, 3, t, ctx, 21504, clip, y, voc, 81)  # noqa: E731
+                    times[k].append(_time(f, iters=2, warmup=1))
+                    outs[k] = f().float()
+                clocks.append(_sclk_mhz())
+        r = {"kernel": "dit_forward_fp8_o_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks,
+             "fused_equals_unfused": bool(torch.equal(outs["four_fused"], outs["four_unfused"])),
+             "rounds_ms": {k: [round(v, 2) for v in times[k]] for k in modes}}
+        for k in modes:
+            r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
+            if k != "off":
+                r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
+                r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
+        for k in ("four_unfused", "four_fused"):
+            r[f"ratio_{k}_vs_three"] = round(r["three_ms"] / r[f"{k}_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os

@@ -209,6 +209,11 @@ class Mx8:
         """a row range (both arrays)"""
         return Mx8(self.q[rows], self.s[rows])
 
+    def cols(self, c0, c1):
+        """columns c0 .. c1 (multiples of 32) of every row (both arrays)"""
+        assert c0 % 32 == 0 and c1 % 32 == 0
+        return Mx8(self.q[:, c0:c1], self.s[:, c0 // 32:c1 // 32])
+
 
 def mxfp8_quant(x, out=None):
     """bf16 x [M, K] (K % 32 == 0) -> Mx8, bit-identical to mxfp8.quantize (sa_mxfp8_quant)."""
@@ -346,31 +351,40 @@ def attn_pack_mxfp8(q, k, v, segs, vcol0, nseg, max_q_len, max_kv_len, heads, bu
 
 
 def attn_fwd_mxfp8(buf, out, segs, vcol0, nseg, max_q_len, heads, o_rows=None, split_tiles=0):
-    """the flash kernel on packed operands (sa_attn_fwd_mxfp8); out bf16 [rows, >= heads * 128]; split_tiles > 0: the
-    last split_tiles (segment, head, 256-query block) tiles as two key halves + a merge (sa_attn_fwd_mxfp8_split,
-    mxfp8_attn.attend_split), the partials in buf's scratch"""
-    _check(out, torch.bfloat16, "attn_fwd_mxfp8.out")
-    assert out.stride(-1) == 1 and buf.heads == heads
+    """the flash kernel on packed operands (sa_attn_fwd_mxfp8); out bf16 [rows, >= heads * 128], or an Mx8
+    [rows, heads * 128] that receives the bf16 output quantised, byte for byte mxfp8_quant of it (sa_attn_fwd_mxfp8_o8:
+    the fp8 self-O mode's O-projection operand); split_tiles > 0: the last split_tiles (segment, head, 256-query
+    block) tiles as two key halves + a merge (sa_attn_fwd_mxfp8_split / _split_o8, mxfp8_attn.attend_split), the
+    partials in buf's scratch"""
+    assert buf.heads == heads
+    if isinstance(out, Mx8):
+        if out.q.shape[1] != heads * 128:
+            raise ValueError(f"attn_fwd_mxfp8: out is {tuple(out.shape)}, the heads have {heads * 128} columns")
+        sfx, o_args = "_o8", (out.q.data_ptr(), out.q.stride(0), out.s.data_ptr(), out.s.stride(0))
+    else:
+        _check(out, torch.bfloat16, "attn_fwd_mxfp8.out")
+        assert out.stride(-1) == 1
+        sfx, o_args = "", (out.data_ptr(), out.stride(0))
     if o_rows is not None:
         assert o_rows.dtype == torch.int32 and o_rows.is_cuda and o_rows.is_contiguous()
+    operands = (buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(), buf.vq.data_ptr(),
+                buf.vs.data_ptr(), buf.Rv, *o_args, segs.data_ptr(), vcol0.data_ptr(), nseg, max_q_len, heads, 128,
+                _p(o_rows))
     if split_tiles:
         work = buf.work(int(split_tiles))
-        call("sa_attn_fwd_mxfp8_split", buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(),
-             buf.vq.data_ptr(), buf.vs.data_ptr(), buf.Rv, out.data_ptr(), out.stride(0), segs.data_ptr(),
-             vcol0.data_ptr(), nseg, max_q_len, heads, 128, _p(o_rows), int(split_tiles), work.data_ptr(),
-             work.numel() * 4, _stream())
+        call("sa_attn_fwd_mxfp8_split" + sfx, *operands, int(split_tiles), work.data_ptr(), work.numel() * 4,
+             _stream())
         return out
-    call("sa_attn_fwd_mxfp8", buf.qq.data_ptr(), buf.qs.data_ptr(), buf.kq.data_ptr(), buf.ks.data_ptr(),
-         buf.vq.data_ptr(), buf.vs.data_ptr(), buf.Rv, out.data_ptr(), out.stride(0), segs.data_ptr(),
-         vcol0.data_ptr(), nseg, max_q_len, heads, 128, _p(o_rows), _stream())
+    call("sa_attn_fwd_mxfp8" + sfx, *operands, _stream())
     return out
 
 
 def attention_mxfp8(q, k, v, out, segs, nseg, max_q_len, heads, vcol0, max_kv_len, buf, head_dim=128, scale=None,
                     o_rows=None, k_mean=True, split_tiles=0):
     """Self-attention on MXFP8 operands (the fp8 attention mode; mxfp8_attn.py is the definition): the K column means
-    of each segment, the operand pack, the flash kernel (split_tiles as attn_fwd_mxfp8).  q, k, v bf16 rows as attention(); vcol0: device int32 per
-    segment and max_kv_len from attn_vcol0's layout (buf.Rv its second result); buf: AttnMx8 owned by the caller."""
+    of each segment, the operand pack, the flash kernel (split_tiles, and out bf16 or Mx8, as attn_fwd_mxfp8).  q, k, v
+    bf16 rows as attention(); vcol0: device int32 per segment and max_kv_len from attn_vcol0's layout (buf.Rv its second
+    result); buf: AttnMx8 owned by the caller."""
     if head_dim != 128:
         raise ValueError("attention_mxfp8: head_dim 128 only")
     km = attn_kmean(k, segs, nseg, heads, buf.kmean, buf.kmean_work) if k_mean else None

@@ -272,6 +272,10 @@ class WanTransformer3DFantasyModel(nn.Module):
         # with _fp8_qkv and _fp8_attn both on, the single-GPU sites write the attention operands where their values are
         # made (_self_attention_rows); False: the mode's GEMM, then _self_attn -- the same output bytes (for the A/B)
         self._fp8_qkv_fused = True
+        self._fp8_o = False  # enable_fp8_o(): the blocks' self-attention O-projection on MXFP8 operands
+        # with _fp8_o and _fp8_attn both on, the single-GPU sites have the flash kernel write the O-projection's operand
+        # (_self_attention_rows); False: bf16 attention output, then the quantiser -- the same bytes (for the A/B)
+        self._fp8_o_fused = True
         self._rstreams = None  # _row_streams(): the HIP streams of the per-CFG-row sequence-parallel schedule
         self._packed = None
         self._ws = {}
@@ -411,10 +415,32 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._packed = None
             self._ws = {}
 
+    def enable_fp8_o(self, enabled=True):
+        """MI355X addition (no counterpart in the reference; changes numerics): the output projection of every DiT
+        block's self-attention (blocks.N.self_attn.o, 1B:413) runs on MXFP8 operands.  Its input is the attention output
+        after its bf16 rounding, quantised by mxfp8.quantize along the row (32-column blocks, four per 128-wide head, none
+        straddling a head); its weight is the bf16 weight quantised by mxfp8.quantize along K; the product is
+        accumulated in fp32; bias, gate and residual follow SA_EPI_RES_F32 as in the bf16 path.  cross_attn.o,
+        cross_attn.q and the vocal projector stay bf16.  Independent of enable_fp8_ffn(), enable_fp8_attention() and
+        enable_fp8_qkv(), every combination works.  With enable_fp8_attention() the single-GPU sites have the flash
+        kernel write the operand itself (sa_attn_fwd_mxfp8_o8: the bytes of the bf16 output quantised, so O never goes
+        to memory as bf16); without it, and at the sequence-parallel sites (whose exchange and panels stay bf16), the
+        bf16 attention output goes through the quantiser first -- one more pass over it, kept so that every combination
+        is correct and not expected to be faster than the bf16 projection.  The operand bytes are the same on every
+        layout.  Toggling drops the packed weights and the workspace, as enable_fp8_qkv does."""
+        enabled = bool(enabled)
+        if enabled and self.dim % 128:
+            raise ValueError(f"enable_fp8_o: dim {self.dim} must be a multiple of 128")
+        if enabled != self._fp8_o:
+            self._fp8_o = enabled
+            self._packed = None
+            self._ws = {}
+
     def _self_attn(self, f, q, k, v, out, segs, kernel=0, split_tiles=0):
         """One self-attention launch of a DiT block over the segment table `segs` (f: the forward's state, whose Lq,
         hg and omap are the launch's query rows per segment, heads and output row map): ops.attention, or with
-        enable_fp8_attention() the K means, the operand pack and the MXFP8 flash kernel (ops.attention_mxfp8);
+        enable_fp8_attention() the K means, the operand pack and the MXFP8 flash kernel (ops.attention_mxfp8; `out` may
+        then be an ops.Mx8, the fp8 self-O mode's operand);
         split_tiles (ops.attn_tail_split, given by the sequence-parallel sites alone; in fp8 mode by the batched one
         alone, see _sp_block_streams) goes to either.  The operand buffers and the split's scratch live in the
         workspace, one set per segment table (the per-row streams run concurrently, each on its own table), allocated
@@ -501,6 +527,8 @@ class WanTransformer3DFantasyModel(nn.Module):
             L.w_v, L.b_v = L.w_qkv[2 * self.dim:], L.b_qkv[2 * self.dim:]
             L.nq, L.nk = f32(p + "self_attn.norm_q.weight"), f32(p + "self_attn.norm_k.weight")
             L.w_o, L.b_o = bf(p + "self_attn.o.weight"), f32(p + "self_attn.o.bias")
+            if self._fp8_o:  # quantised along K on the GPU (= mxfp8.quantize), the bf16 copy dropped
+                L.w_o = ops.mxfp8_quant(L.w_o)
             L.n3w, L.n3b = f32(p + "norm3.weight"), f32(p + "norm3.bias")
             c = p + "cross_attn."
             L.w_cq, L.b_cq = bf(c + "q.weight"), f32(c + "q.bias")
@@ -572,6 +600,8 @@ class WanTransformer3DFantasyModel(nn.Module):
                 ws.modq = ops.Mx8.empty(M, dim, dev)
             if self._fp8_ffn:  # the FFN's hidden activations as MXFP8
                 ws.ffn = ops.Mx8.empty(M, self.ffn_dim, dev)
+            if self._fp8_o:  # the self-attention output as MXFP8 (the O-projection's input)
+                ws.attq = ops.Mx8.empty(M, dim, dev)
             self._ws = {key: ws}  # keep one shape at a time
         return ws
 
@@ -755,24 +785,47 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._self_attn(f, ex.q, f.k, f.v, ex.obuf, R.self_attn, kernel=kernel, split_tiles=split_tiles)
         return ex.tokens(R.rows)
 
+    def _o_proj(self, f, L, R, e, att):
+        """The O-projection + gated residual (1B:677-679) of the rows R: bf16 `att` through the bf16 GEMM, or with
+        enable_fp8_o() the MXFP8 GEMM on R.attq -- `att` quantised into it first, or att = None: it already holds the
+        operand (the flash kernel, or _sp_o_proj's panels, wrote it)"""
+        if not self._fp8_o:
+            return ops.linear(att, L.w_o, L.b_o, ops.EPI_RES_F32, out=R.x, residual=R.x, gate=e[:, 2],
+                              rows_per_batch=f.Lc)
+        if att is not None:
+            ops.mxfp8_quant(att, out=R.attq)
+        return ops.linear_mxfp8(R.attq, L.w_o, L.b_o, ops.EPI_RES_F32, out=R.x, residual=R.x, gate=e[:, 2],
+                                rows_per_batch=f.Lc)
+
     def _sp_o_proj(self, f, L, em, b, back):
         """the head outputs `back` of the selected rows received, their O-projection over the column panels +
-        gated residual (1B:677-679)"""
+        gated residual (1B:677-679).  With enable_fp8_o() each bf16 panel (whole heads) is quantised into its columns
+        of R.attq -- the single-GPU operand's bytes -- and the MXFP8 GEMM reads that one matrix"""
         R, e = self._sel(f, b, em)
         back.wait()
         a0, pnl = f.ex.panels(R.rows)
-        ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=R.x, residual=R.x, gate=e[:, 2], rows_per_batch=f.Lc,
-                   a_panels=pnl)
+        if not self._fp8_o:
+            return ops.linear(a0, L.w_o, L.b_o, ops.EPI_RES_F32, out=R.x, residual=R.x, gate=e[:, 2],
+                              rows_per_batch=f.Lc, a_panels=pnl)
+        pc, ps = pnl
+        for p in range(self.dim // pc):
+            panel = a0.as_strided(a0.shape, a0.stride(), a0.storage_offset() + p * ps)
+            ops.mxfp8_quant(panel, out=R.attq.cols(p * pc, (p + 1) * pc))
+        self._o_proj(f, L, R, e, None)
 
     def _self_attention_rows(self, f, L, em, b=None, normed=False):
         """The self-attention half of a block (1B:675-679) on the single-GPU layout, for all CFG rows or row 0 (the
         shared first block): LN + modulate (unless `normed`), q|k (+ v as V^T for kernel 3, or q|k|v rows), RMSNorm +
         RoPE, attention, O-projection + gated residual into x.  With enable_fp8_qkv() and enable_fp8_attention() (and
         _fp8_qkv_fused) the fused chain: q|k GEMM, the V GEMM writing the V^T operand, RMSNorm + RoPE writing the Q
-        operand, K means, K pack, the MXFP8 flash kernel."""
+        operand, K means, K pack, the MXFP8 flash kernel.  With enable_fp8_o() and enable_fp8_attention() (and
+        _fp8_o_fused) either flash launch writes the O-projection's MXFP8 operand instead of bf16 rows."""
         dim, H_, ws, Lc, Lp = self.dim, self.num_heads, f.ws, f.Lc, f.Lp
         R, e = self._sel(f, b, em)
-        nb, segs, xr, mod, qkv, att = len(R.rows), R.self_attn, R.x, R.mod, R.qkv, R.att
+        nb, segs, mod, qkv, att = len(R.rows), R.self_attn, R.mod, R.qkv, R.att
+        o8 = self._fp8_o and self._fp8_attn and self._fp8_o_fused
+        if o8:
+            att = R.attq
         if not normed:
             self._norm1(f, R, e)
         if self._fp8_qkv and self._fp8_attn and self._fp8_qkv_fused:
@@ -803,7 +856,7 @@ class WanTransformer3DFantasyModel(nn.Module):
             with self._span(rows=nb, batch=f.B):
                 self._self_attn(f, qkv[:, :dim], qkv[:, dim:2 * dim], qkv[:, 2 * dim:], att, segs,
                                 kernel=self.attn_kernel)
-        ops.linear(att, L.w_o, L.b_o, ops.EPI_RES_F32, out=xr, residual=xr, gate=e[:, 2], rows_per_batch=Lc)
+        self._o_proj(f, L, R, e, None if o8 else att)
 
     def _cross_attention(self, f, L, b):
         """cross-attention of the selected rows: text + image + per-frame vocal (1B:534-605, 684), its output
@@ -1068,7 +1121,8 @@ class WanTransformer3DFantasyModel(nn.Module):
         def views(rows):  # the workspace rows of the CFG rows `rows`, sliced once per forward
             rs = slice(rows.start * Lc, rows.stop * Lc)
             return SimpleNamespace(rows=rows, x=ws.x[rs], mod=ws.mod[rs], qkv=ws.qkv[rs], att=ws.att[rs],
-                                   ffn=ws.ffn[rs], modq=ws.modq[rs] if hasattr(ws, "modq") else None)
+                                   ffn=ws.ffn[rs], modq=ws.modq[rs] if hasattr(ws, "modq") else None,
+                                   attq=ws.attq[rs] if hasattr(ws, "attq") else None)
         f.all, f.row = views(range(B)), [views(range(b, b + 1)) for b in range(B)]
         if self._sp_enabled:
             plan = sp.make_plan(f.NS, rank, self.num_heads)
