@@ -364,6 +364,25 @@ int sa_flow_step(const void* latents_all, void* pred_all, const void* noise, int
                  int64_t HW, int start, float dsigma, float audio_scale, float text_scale, int overlap, int prev_end,
                  const float* weights, int blend, void* stream);
 
+/* CFG combine + one FlowUniPCMultistepScheduler step (wan/utils/fm_solvers_unipc.py: solver_order 2, bh2, x0
+ * prediction, flow_prediction) + overlap blend + scatter of one window; sizes, frames and the blend arguments as
+ * sa_flow_step.  v is sa_flow_step's bf16 CFG chain; then in fp32, every op rounded once (no fma):
+ *   m  = x - sigma v                          x = latents_all
+ *   xc = ((c0 xhat + c1 m0) + c2 m1) + c3 m   corrector 2;  corrector 1: no m1 term (m1 is not read);  0: xc = x
+ *   xn = (p0 xc + p1 m) + p2 m0               predictor 2;  predictor 1: no m0 term
+ * blending, q = q w + q_prev (1 - w), w = bf16(weights[f]), for q in (xn, xc, m) against what the step's previous
+ * window left in pred_all / xhat_new / m_new at frame (prev_end - overlap + f) % T.  pred_all = bf16(xn), xhat_new =
+ * xc, m_new = m.  xhat / m0 / m1 / xhat_new / m_new: fp32 [C, T, HW]; the three read ones belong to the previous
+ * step and stay unwritten (the windows of a step overlap), so the caller rotates the buffers per step.  The scalars
+ * are FlowUniPCMultistepScheduler.step_coefficients' (scheduler.py).  SA_ERR_ARG, with no launch, also for: a null
+ * xhat_new / m_new, a null xhat or m0 with corrector != 0, a null m1 with corrector == 2, a null m0 with predictor
+ * == 2, corrector outside {0, 1, 2}, predictor outside {1, 2}, a non-finite scalar. */
+int sa_unipc_step(const void* latents_all, void* pred_all, const void* noise, int R, int C, int T, int Fw,
+                  int64_t HW, int start, float sigma, float c0, float c1, float c2, float c3, float p0, float p1,
+                  float p2, int corrector, int predictor, float audio_scale, float text_scale, int overlap,
+                  int prev_end, const float* weights, int blend, const float* xhat, const float* m0, const float* m1,
+                  float* xhat_new, float* m_new, void* stream);
+
 /* out[r] = idx[r] >= 0 ? in[idx[r]] : 0  (split_tensor_with_padding, vocal_projector_fantasy.py:81-131).
  * nrows == 0 is a no-op that returns SA_OK (as n == 0 of sa_fill_f32 / sa_cast_f32_bf16); nrows < 0 or
  * row_bytes <= 0 is SA_ERR_ARG. */

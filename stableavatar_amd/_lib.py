@@ -49,6 +49,7 @@ SIGNATURES = {
     "sa_attn_small_split": "pppppiiiiillllfiplp",
     "sa_attn_cross3": "plpplipplippliiiipliiifp",
     "sa_flow_step": "pppiiiilifffiipip",
+    "sa_unipc_step": "pppiiiiliffffffffiiffiipipppppp",
     "sa_gather_rows": "plpipllp",
     "sa_fill_f32": "plfp",
     "sa_cast_f32_bf16": "pplp",

@@ -5,8 +5,11 @@
 //  sa_small_linear_f32 : fp32 Linear for the M<=8-row time MLPs (fp32 autocast)          (1B:986-990)
 //  sa_mod_add          : per-layer AdaLN vectors  e = modulation + e0                    (1B:672,721)
 //  sa_flow_step        : CFG combine + FlowMatch Euler step + overlap blend + scatter    (pipeline:751-779)
+//  sa_unipc_step       : CFG combine + FlowUniPC step (order 2, bh2) + overlap blend + scatter  (fm_solvers_unipc.py)
 //  sa_gather_rows      : row gather with zero rows (vocal frame split)                   (vocal_projector_fantasy.py:81-131)
 //  sa_fill_f32, sa_cast_f32_bf16
+#include <cmath>
+
 #include "common.h"
 
 namespace {
@@ -109,6 +112,23 @@ __global__ void mod_add_kernel(const float* mod, const float* e, long eb, long e
   out[idx] = mod[((long)l * J + j) * C + c] + e[b * eb + j * ej + c];
 }
 
+// v = u + a*(d-u) + t*(c-d) of the noise_pred rows [R, C, Fw, HW] at element nidx (R == 1: the row itself), shared
+// by the two sampler steps
+__device__ __forceinline__ float cfg_combine(const bf16* noise, int R, int C, int Fw, long HW, long nidx,
+                                             float audio_scale, float text_scale) {
+#pragma clang fp contract(off)
+  if (R == 3) {
+    // reference math is bf16 elementwise; round each partial like torch does on bf16 tensors
+    const float u = bf2f(noise[nidx]);
+    const float d = bf2f(noise[(long)C * Fw * HW + nidx]);
+    const float cc = bf2f(noise[2L * C * Fw * HW + nidx]);
+    const float t1 = bf2f(f2bf(bf2f(f2bf(d - u)) * audio_scale));
+    const float t2 = bf2f(f2bf(bf2f(f2bf(cc - d)) * text_scale));
+    return bf2f(f2bf(bf2f(f2bf(u + t1)) + t2));
+  }
+  return bf2f(noise[nidx]);
+}
+
 // One sampler step for one window (pipeline:751-779):
 //   v   = u + a*(d-u) + t*(c-d)                      (bf16 noise_pred rows u/d/c)   if cfg
 //   x1  = bf16( x0 + bf16(bf16(sigma_next - sigma) * v) )  (FlowMatchEuler step, sample upcast to fp32; torch casts
@@ -130,18 +150,7 @@ __global__ void flow_step_kernel(const bf16* latents_all, bf16* pred_all, const 
   const long p = idx % HW;
   const int f = (idx / HW) % Fw, c = idx / (HW * Fw);
   const long nidx = ((long)c * Fw + f) * HW + p;
-  float v;
-  if (R == 3) {
-    // reference math is bf16 elementwise; round each partial like torch does on bf16 tensors
-    const float u = bf2f(noise[nidx]);
-    const float d = bf2f(noise[(long)C * Fw * HW + nidx]);
-    const float cc = bf2f(noise[2L * C * Fw * HW + nidx]);
-    const float t1 = bf2f(f2bf(bf2f(f2bf(d - u)) * audio_scale));
-    const float t2 = bf2f(f2bf(bf2f(f2bf(cc - d)) * text_scale));
-    v = bf2f(f2bf(bf2f(f2bf(u + t1)) + t2));
-  } else {
-    v = bf2f(noise[nidx]);
-  }
+  const float v = cfg_combine(noise, R, C, Fw, HW, nidx, audio_scale, text_scale);
   const int fa = (start + f) % T;
   const float x0 = bf2f(latents_all[((long)c * T + fa) * HW + p]);
   // 0-d fp32 * bf16 tensor -> bf16, the 0-d operand cast to bf16 first; then + fp32 sample
@@ -155,6 +164,56 @@ __global__ void flow_step_kernel(const bf16* latents_all, bf16* pred_all, const 
     x1 = bf2f(f2bf(a1 + a2));
   }
   pred_all[((long)c * T + fa) * HW + p] = f2bf(x1);
+}
+
+// One FlowUniPCMultistepScheduler step (order 2, bh2, x0 prediction) for one window, indexed as flow_step_kernel:
+//   v  = the CFG combine above (bf16 chain); everything after it is fp32, each op rounded once, no contraction
+//   m  = x - sigma*v                                              (convert_model_output; x = latents_all, bf16)
+//   xc = ((c0*xh + c1*m0) + c2*m1) + c3*m   corrector on (order 2; order 1 has no m1 term), else xc = x
+//   xn = (p0*xc + p1*m) + p2*m0             predictor order 2 (order 1 has no m0 term)
+//   q[j] = q[j]*w_j + q_prev[j]*(1-w_j)     for q in (xn, xc, m) on the first `overlap` frames when blending, against
+//                                           what the previous window of this step wrote to pred_all / xh_new / m_new
+//   pred_all = bf16(xn), xh_new = xc, m_new = m
+// xh / m0 / m1: the previous step's corrected sample and converted outputs, fp32 [C, T, HW], read only; every window
+// of a step reads them and writes xh_new / m_new, which the caller rotates per step as it does latents / pred.
+__global__ void unipc_step_kernel(const bf16* latents_all, bf16* pred_all, const bf16* noise, int R, int C, int T,
+                                  int Fw, long HW, int start, float sigma, float c0, float c1, float c2, float c3,
+                                  float p0, float p1, float p2, int corrector, int predictor, float audio_scale,
+                                  float text_scale, int overlap, int prev_end, const float* wts, int blend,
+                                  const float* xh, const float* m0p, const float* m1p, float* xh_new, float* m_new) {
+#pragma clang fp contract(off)
+  const long n = (long)C * Fw * HW;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const long p = idx % HW;
+  const int f = (idx / HW) % Fw, c = idx / (HW * Fw);
+  const long nidx = ((long)c * Fw + f) * HW + p;
+  const float v = cfg_combine(noise, R, C, Fw, HW, nidx, audio_scale, text_scale);
+  const int fa = (start + f) % T;
+  const long o = ((long)c * T + fa) * HW + p;
+  const float x = bf2f(latents_all[o]);
+  float m = x - sigma * v;
+  const float m0 = (corrector || predictor == 2) ? m0p[o] : 0.f;
+  float xc = x;
+  if (corrector) {
+    xc = c0 * xh[o] + c1 * m0;
+    if (corrector == 2) xc = xc + c2 * m1p[o];
+    xc = xc + c3 * m;
+  }
+  float xn = p0 * xc + p1 * m;
+  if (predictor == 2) xn = xn + p2 * m0;
+  if (blend && f < overlap) {
+    const float w = bf2f(f2bf(wts[f]));
+    const float w1 = 1.f - w;
+    const int fp = (prev_end - overlap + f) % T;
+    const long q = ((long)c * T + fp) * HW + p;
+    xn = xn * w + bf2f(pred_all[q]) * w1;
+    xc = xc * w + xh_new[q] * w1;
+    m = m * w + m_new[q] * w1;
+  }
+  pred_all[o] = f2bf(xn);
+  xh_new[o] = xc;
+  m_new[o] = m;
 }
 
 __global__ void gather_rows_kernel(const char* in, long in_row_bytes, const int* idx, int nrows, char* out,
@@ -247,6 +306,28 @@ extern "C" int sa_flow_step(const void* latents_all, void* pred_all, const void*
   hipLaunchKernelGGL(flow_step_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)latents_all, (bf16*)pred_all, (const bf16*)noise, R, C, T, Fw, HW, start, dsigma,
                      audio_scale, text_scale, overlap, prev_end, weights, blend);
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+extern "C" int sa_unipc_step(const void* latents_all, void* pred_all, const void* noise, int R, int C, int T, int Fw,
+                             int64_t HW, int start, float sigma, float c0, float c1, float c2, float c3, float p0,
+                             float p1, float p2, int corrector, int predictor, float audio_scale, float text_scale,
+                             int overlap, int prev_end, const float* weights, int blend, const float* xhat,
+                             const float* m0, const float* m1, float* xhat_new, float* m_new, void* stream) {
+  if (!latents_all || !pred_all || !noise || (R != 1 && R != 3) || Fw > T) return SA_ERR_ARG;
+  if (C <= 0 || T <= 0 || Fw <= 0 || HW <= 0 || start < 0) return SA_ERR_ARG;
+  if (blend && (!weights || overlap <= 0 || overlap > Fw || prev_end < overlap)) return SA_ERR_ARG;
+  if (corrector < 0 || corrector > 2 || (predictor != 1 && predictor != 2)) return SA_ERR_ARG;
+  if (!xhat_new || !m_new || (corrector && (!xhat || !m0)) || (corrector == 2 && !m1) || (predictor == 2 && !m0))
+    return SA_ERR_ARG;
+  for (float s : {sigma, c0, c1, c2, c3, p0, p1, p2, audio_scale, text_scale})
+    if (!std::isfinite(s)) return SA_ERR_ARG;
+  const long n = (long)C * Fw * HW;
+  hipLaunchKernelGGL(unipc_step_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16*)latents_all, (bf16*)pred_all, (const bf16*)noise, R, C, T, Fw, HW, start, sigma, c0,
+                     c1, c2, c3, p0, p1, p2, corrector, predictor, audio_scale, text_scale, overlap, prev_end, weights,
+                     blend, xhat, m0, m1, xhat_new, m_new);
   SA_LAUNCH_CHECK();
   return SA_OK;
 }

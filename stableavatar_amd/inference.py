@@ -117,6 +117,12 @@ def parse_args(argv=None):
                         "and has no counterpart in the reference. With --fp8_attn the flash kernel writes the "
                         "projection's MXFP8 operand itself; without it the bf16 output takes one more quantiser pass "
                         "(DESIGN.md, fp8 self-O).")
+    p.add_argument("--sampler", type=str, default="euler", choices=("euler", "unipc"),
+                   help="euler: FlowMatchEulerDiscreteScheduler, the reference pipeline's sampler (default). unipc: "
+                        "FlowUniPCMultistepScheduler (wan/utils/fm_solvers_unipc.py: order 2, bh2), the multistep "
+                        "solver Wan is normally sampled with, one fused sa_unipc_step launch per window; its own sigma "
+                        "table, second order on an analytic ODE. Quality at fewer --sample_steps on real checkpoints "
+                        "is unmeasured (DESIGN.md, UniPC sampler).")
     p.add_argument("--window_parallel", action="store_true",
                    help="multi-GPU: spread the sliding windows of each step over the ranks instead of sequence "
                         "parallelism (long clips, SURVEY.md §8(e))")
@@ -211,7 +217,7 @@ def main(argv=None):
 
     from .encoders import CLIPModel, WanT5EncoderModel
     from .pipeline import WanI2VTalkingInferenceLongPipeline
-    from .scheduler import FlowMatchEulerDiscreteScheduler
+    from .scheduler import FlowMatchEulerDiscreteScheduler, FlowUniPCMultistepScheduler
     from .teacache import get_teacache_coefficients
     from .transformer import WanTransformer3DFantasyModel
     from .vae import AutoencoderKLWan
@@ -260,9 +266,13 @@ def main(argv=None):
     sk = dict(config.get("scheduler_kwargs", {}))
     if args.sample_shift is not None:
         sk["shift"] = args.sample_shift
-    scheduler = FlowMatchEulerDiscreteScheduler(**{k: v for k, v in sk.items() if k in (
-        "num_train_timesteps", "shift", "use_dynamic_shifting", "base_shift", "max_shift", "base_image_seq_len",
-        "max_image_seq_len")})
+    if args.sampler == "unipc":
+        scheduler = FlowUniPCMultistepScheduler(**{k: v for k, v in sk.items() if k in (
+            "num_train_timesteps", "shift", "use_dynamic_shifting")})
+    else:
+        scheduler = FlowMatchEulerDiscreteScheduler(**{k: v for k, v in sk.items() if k in (
+            "num_train_timesteps", "shift", "use_dynamic_shifting", "base_shift", "max_shift", "base_image_seq_len",
+            "max_image_seq_len")})
     pipeline = WanI2VTalkingInferenceLongPipeline(tokenizer=tokenizer, text_encoder=text_encoder, vae=vae,
                                                   transformer=transformer3d, clip_image_encoder=clip_image_encoder,
                                                   scheduler=scheduler, wav2vec_processor=wav2vec_processor,

@@ -7,7 +7,8 @@ on together with the fp8 FFN; qkvfp8 = the self-attention's operand chain (Layer
 fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn / attn+ffn+qkv unfused / fused;
 ofp8 = the MXFP8 flash kernel + the self-attention O-projection in bf16 and with the fp8 self-O mode unfused and fused,
 ditfp8o = the whole forward off / the three modes / the three + fp8 self-O unfused / fused;
-attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16.
+attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16;
+unipc = sa_unipc_step beside sa_flow_step at config 2's latent shape.
 gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ks's one-tile kernel (the baseline arm) against its persistent kernel and
 against the one-tile kernel with the split K step (kstep=2) on their GEMM shapes, and ditfp8qkv has
 variants that run every MXFP8 GEMM of the forward on the persistent kernel and on the one-barrier K step."""
@@ -307,6 +308,8 @@ def main(which=("gemm", "attn")):
     if "ditfp8" in which:  # whole-forward A/B of enable_fp8_ffn(), interleaved
         res.append(bench_dit(fp8_ab=True))
         print(json.dumps(res[-1]), flush=True)
+    if "unipc" in which:  # the UniPC sampler step beside the Euler one at config 2's latent shape, interleaved
+        res.extend(bench_unipc())
     if "ditvar" in which:  # in-situ A/B of attention variants inside full DiT forwards (interleaved)
         import os
         avars = tuple(int(v) for v in os.environ.get("SA_KB_AVARS", "1").split(","))
@@ -321,6 +324,42 @@ def _sclk_mhz():
         return int(torch.cuda.clock_rate())
     except Exception:  # noqa: BLE001
         return None
+
+
+def bench_unipc(C=16, T=21, H=64, W=64, R=3, rounds=5):
+    """sa_unipc_step (a middle step: corrector and predictor at order 2, all state read) beside sa_flow_step on one
+    whole-clip window of config 2's latents [16, 21, 64, 64], R = 3 noise rows, same process, interleaved rounds,
+    median of `rounds` with every round kept; 200 launches per timing so that a window is milliseconds, not one
+    launch.  bytes = what each kernel has to move per launch: Euler 3 x 2 (noise) + 2 (x) + 2 (pred) = 10 B per
+    element, UniPC + 3 x 4 (xhat, m0, m1) + 2 x 4 (new xhat, new m) = 30 B."""
+    from .scheduler import FlowUniPCMultistepScheduler
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    lat = torch.randn(1, C, T, H, W, device=dev, generator=g).bfloat16()
+    pred = torch.empty_like(lat)
+    noise = torch.randn(R, C, T, H, W, device=dev, generator=g).bfloat16()
+    st = [torch.randn(1, C, T, H, W, device=dev, generator=g) for _ in range(5)]
+    sched = FlowUniPCMultistepScheduler(1000, shift=5.0)
+    sched.set_timesteps(50)
+    k = sched.step_coefficients(25)
+    assert (k.corrector, k.predictor) == (2, 2)
+    dsig = float(sched.sigmas[26]) - float(sched.sigmas[25])
+    fns = {"flow_step": lambda: ops.flow_step(lat, pred, noise, 0, dsig, 5.0, 3.0, 0, 0, None, False),
+           "unipc_step": lambda: ops.unipc_step(lat, pred, noise, 0, k, 5.0, 3.0, 0, 0, None, False, *st)}
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(rounds):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=200, warmup=5))
+        clocks.append(_sclk_mhz())
+    n_el = C * T * H * W
+    by = {"flow_step": (2 * R + 2 + 2) * n_el, "unipc_step": (2 * R + 2 + 2 + 3 * 4 + 2 * 4) * n_el}
+    r = {"kernel": "sampler_step", "shape": [C, T, H, W], "noise_rows": R, "sclk_mhz": clocks}
+    for n in fns:
+        ms = sorted(times[n])[rounds // 2]
+        r.update({f"{n}_us": round(1e3 * ms, 2), f"{n}_rounds_us": [round(1e3 * t, 2) for t in times[n]],
+                  f"{n}_bytes": by[n], f"{n}_gbps": round(by[n] / ms / 1e6, 1)})
+    print(json.dumps(r), flush=True)
+    return [r]
 
 
 def bench_fp8_attn(L=21504, H=12, B=3):

@@ -48,6 +48,8 @@ def classify(name: str, args) -> str:
         return "vae_other"
     if name == "sa_flow_step":
         return "flow_step"
+    if name == "sa_unipc_step":
+        return "unipc_step"
     return "other"
 
 

@@ -532,6 +532,25 @@ def flow_step(latents_all, pred_all, noise, start, dsigma, audio_scale, text_sca
          float(dsigma), float(audio_scale), float(text_scale), overlap, prev_end, _p(weights), int(blend), _stream())
 
 
+def unipc_step(latents_all, pred_all, noise, start, coef, audio_scale, text_scale, overlap, prev_end, weights, blend,
+               xhat, m0, m1, xhat_new, m_new):
+    """One FlowUniPCMultistepScheduler step of one window (sa_unipc_step); coef = scheduler.step_coefficients(i).
+    xhat / m0 / m1 (the previous step's state; None where coef's orders do not read them) and xhat_new / m_new are
+    fp32 tensors of the latents' shape."""
+    C, T = latents_all.shape[1], latents_all.shape[2]
+    R, Fw = noise.shape[0], noise.shape[2]
+    HW = noise.shape[3] * noise.shape[4]
+    for t in (xhat, m0, m1, xhat_new, m_new):
+        if t is not None:
+            _check(t, torch.float32, "unipc_step state")
+            if t.numel() != latents_all.numel() or not t.is_contiguous():
+                raise ValueError("unipc_step: a state buffer is a contiguous fp32 tensor of the latents' shape")
+    call("sa_unipc_step", latents_all.data_ptr(), pred_all.data_ptr(), noise.data_ptr(), R, C, T, Fw, HW, start,
+         *(float(v) for v in coef[:8]), int(coef.corrector), int(coef.predictor), float(audio_scale),
+         float(text_scale), overlap, prev_end, _p(weights), int(blend), _p(xhat), _p(m0), _p(m1), _p(xhat_new),
+         _p(m_new), _stream())
+
+
 def gather_rows(inp, idx, out):
     row_bytes = inp.shape[-1] * inp.element_size()
     call("sa_gather_rows", inp.data_ptr(), inp.stride(0) * inp.element_size(), idx.data_ptr(), idx.shape[0],

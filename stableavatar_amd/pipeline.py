@@ -4,7 +4,8 @@ wan/pipeline/wan_inference_long_pipeline.py).
 Same constructor and `__call__` arguments.  The hot path -- the sliding-window x 3-way-CFG denoise
 loop (:703-790) and the VAE decode (:793-796, :424-430) -- runs on the HIP kernels:
 WanTransformer3DFantasyModel.forward_window per window, then ONE fused sa_flow_step kernel per
-window for CFG combine + Euler step + overlap blend + scatter.  The once-per-call encoders (T5,
+window for CFG combine + Euler step + overlap blend + scatter (sa_unipc_step in its place when the scheduler is a
+FlowUniPCMultistepScheduler).  The once-per-call encoders (T5,
 CLIP, VAE-encode of the reference frame) are called exactly as the reference does when given, or
 their outputs can be passed directly (`prompt_embeds`/`negative_prompt_embeds`, `clip_context`,
 `y`).  wav2vec features depend only on the audio slice of a window, so they are computed once per
@@ -21,6 +22,48 @@ import numpy as np
 import torch
 
 from . import ops
+from .scheduler import FlowUniPCMultistepScheduler
+
+
+class _EulerStep:
+    """the sampler step of one window under FlowMatchEulerDiscreteScheduler: one sa_flow_step launch"""
+
+    def __init__(self, sigmas):
+        self.sig = [float(s) for s in sigmas]
+
+    def window(self, i, lat, pred, noise, start, audio_scale, text_scale, overlap, prev_end, wts, blend):
+        ops.flow_step(lat, pred, noise, start, self.sig[i + 1] - self.sig[i], audio_scale, text_scale, overlap,
+                      prev_end, wts, blend)
+
+    def end_step(self):
+        pass
+
+
+class _UniPCStep:
+    """the sampler step of one window under FlowUniPCMultistepScheduler: one sa_unipc_step launch.  The solver's
+    history -- the corrected sample and the last two converted model outputs, fp32, the latents' shape -- is read by
+    every window of a step and written anew, so it ping-pongs per step beside lat / pred: two buffers for the
+    corrected sample, three for the outputs (new -> m0 -> m1).  The coefficients come from the scheduler's CPU sigma
+    table: no host synchronisation."""
+
+    def __init__(self, scheduler, lat, n_steps):
+        if scheduler.num_inference_steps != n_steps:
+            raise ValueError(f"the UniPC scheduler is set for {scheduler.num_inference_steps} steps, denoise got "
+                             f"{n_steps} timesteps: call set_timesteps first")
+        self.coef = [scheduler.step_coefficients(i) for i in range(n_steps)]
+        new = lambda: torch.empty(lat.shape, device=lat.device, dtype=torch.float32)  # noqa: E731
+        self.xh = [new(), new()]        # [previous step's, this step's]
+        self.m = [new(), new(), new()]  # [this step's, previous step's (m0), the one before (m1)]
+
+    def window(self, i, lat, pred, noise, start, audio_scale, text_scale, overlap, prev_end, wts, blend):
+        k = self.coef[i]
+        ops.unipc_step(lat, pred, noise, start, k, audio_scale, text_scale, overlap, prev_end, wts, blend,
+                       self.xh[0] if k.corrector else None, self.m[1] if k.corrector or k.predictor == 2 else None,
+                       self.m[2] if k.corrector == 2 else None, self.xh[1], self.m[0])
+
+    def end_step(self):
+        self.xh.reverse()
+        self.m = [self.m[2], self.m[0], self.m[1]]
 
 
 def window_schedule(infer_length, frames_per_batch, overlap):
@@ -212,10 +255,13 @@ class WanI2VTalkingInferenceLongPipeline:
         # (forward_window shared_rows); checked once per call.  SA_CFG_SHARED=0 computes every row (A/B)
         self._shared_rows = (cfg and os.environ.get("SA_CFG_SHARED", "1") != "0"
                              and bool((yb[1:] == yb[:1]).all()))
-        sig = [float(s) for s in sigmas]
+        if isinstance(self.scheduler, FlowUniPCMultistepScheduler):
+            sampler = _UniPCStep(self.scheduler, lat, len(timesteps))
+        else:
+            sampler = _EulerStep(sigmas)
         if self.window_group is not None:
             return self._denoise_window_parallel(lat, pred, yb, context, clip_context, window_features, timesteps,
-                                                 sig, wins, wts, cfg, fpb, clip_length, seq_len, overlap,
+                                                 sampler, wins, wts, cfg, fpb, clip_length, seq_len, overlap,
                                                  text_guide_scale, audio_guide_scale, callback)
         for i, t in enumerate(timesteps):
             pred.zero_()
@@ -226,14 +272,15 @@ class WanI2VTalkingInferenceLongPipeline:
                                                         clip_context, yb[:, :, :Fw], window_features[(s, e)],
                                                         clip_length, shared_rows=self._shared_rows)
                 blend = s != 0 and i != 0
-                ops.flow_step(lat, pred, noise, s, sig[i + 1] - sig[i], audio_guide_scale or 0.0,
-                              text_guide_scale or 0.0, overlap if blend else 0, pe, wts if blend else None, blend)
+                sampler.window(i, lat, pred, noise, s, audio_guide_scale or 0.0, text_guide_scale or 0.0,
+                               overlap if blend else 0, pe, wts if blend else None, blend)
             lat, pred = pred, lat
+            sampler.end_step()
             if callback is not None:
                 callback(i, t, lat)
         return lat
 
-    def _denoise_window_parallel(self, lat, pred, yb, context, clip_context, window_features, timesteps, sig, wins,
+    def _denoise_window_parallel(self, lat, pred, yb, context, clip_context, window_features, timesteps, sampler, wins,
                                  wts, cfg, fpb, clip_length, seq_len, overlap, text_guide_scale, audio_guide_scale,
                                  callback):
         import torch.distributed as dist
@@ -268,9 +315,10 @@ class WanI2VTalkingInferenceLongPipeline:
                 p_.wait()
             for k, (s, e, pe) in enumerate(wins):
                 blend = s != 0 and i != 0
-                ops.flow_step(lat, pred, view(k), s, sig[i + 1] - sig[i], audio_guide_scale or 0.0,
-                              text_guide_scale or 0.0, overlap if blend else 0, pe, wts if blend else None, blend)
+                sampler.window(i, lat, pred, view(k), s, audio_guide_scale or 0.0, text_guide_scale or 0.0,
+                               overlap if blend else 0, pe, wts if blend else None, blend)
             lat, pred = pred, lat
+            sampler.end_step()
             if callback is not None:
                 callback(i, t, lat)
         return lat
