@@ -119,6 +119,23 @@ int sa_attn_fwd_split(const void* q, const void* k, const void* v, void* o, cons
                       int64_t o_stride, float scale, int accumulate, const int32_t* o_rows, int split_tiles, void* work,
                       int64_t work_bytes, void* stream);
 
+/* sa_attn_fwd_map over a block list: query block qb (the 256-query tile qb of every segment, for every head) attends
+ * only the 64-key blocks blk_idx[blk_ptr[qb] .. blk_ptr[qb + 1]) of its segment.  blk_ptr = device int32
+ * [n_qblocks + 1], non-decreasing from 0; blk_idx = device int32, per query block strictly ascending block numbers
+ * relative to the segment's kv_row0, each < ceil(kv_len / 64); n_qblocks must equal ceil(max_q_len / 256).  One table
+ * serves every segment and head of the launch (the self-attention segments of a forward share one geometry);
+ * stableavatar_amd/sparse_attn.py builds and validates tables on the host -- the device contents are not checked here.
+ * kernel: 0 or 1 = the 8-wave row-major kernel, 3 = the 8-wave V^T kernel (v as for sa_attn_fwd_ex kernel 3); any
+ * other value, a NULL or misaligned table or another n_qblocks returns 1.  No 4-wave and no key-split form.
+ * Numerical contract: sa_attn_fwd's, applied to the keys of the listed blocks in ascending order (the tail block
+ * masked past kv_len as ever).  With every block listed the output is byte-identical to sa_attn_fwd_map with the same
+ * kernel; unlisted blocks of k and v are never read; an empty list behaves as kv_len == 0 (zeros; nothing added when
+ * accumulating). */
+int sa_attn_fwd_sparse(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int nseg,
+                       int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                       int64_t o_stride, float scale, int accumulate, int kernel, const int32_t* o_rows,
+                       const int32_t* blk_ptr, const int32_t* blk_idx, int n_qblocks, void* stream);
+
 /* The three attentions of WanI2VTalkingCrossAttention.forward (1B:556-603) in one launch: per batch
  * row b, queries q[b*q_len + i] attend to text k/v rows [b*t_len, +t_len), image rows [b*i_len, +i_len)
  * and the vocal rows of their latent frame, [(b*n_frames + f)*nper, +nper) with

@@ -23,6 +23,7 @@ SIGNATURES = {
     "sa_attn_fwd_ex": "pppppiiiillllfiip",
     "sa_attn_fwd_map": "pppppiiiillllfiipp",
     "sa_attn_fwd_split": "pppppiiiillllfipiplp",
+    "sa_attn_fwd_sparse": "pppppiiiillllfiipppip",
     "sa_layernorm_mod": "pliplipppplpiiifp",
     "sa_mxfp8_quant": "plplpliip",
     "sa_layernorm_mod_mxfp8": "pliplplppppliiifp",

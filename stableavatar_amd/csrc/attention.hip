@@ -38,6 +38,17 @@ struct AttnArgs {
   float* work;
 };
 
+// block-sparse launches (attn_fwd_v6_sparse_kernel, attn_fwd_v6t_sparse_kernel): query block qb of every segment and
+// head runs the 64-key blocks blk_idx[blk_ptr[qb] .. blk_ptr[qb + 1]) of its segment, ascending, instead of all of them
+struct AttnSparseArgs : AttnArgs {
+  const int* blk_ptr;
+  const int* blk_idx;
+};
+// a table word at a wave-uniform address: the constant address space makes it one scalar load (s_load_dword)
+__device__ __forceinline__ int sload(const int* p) {
+  return *(const __attribute__((address_space(4))) int*)(uintptr_t)p;
+}
+
 constexpr int D = 128;
 constexpr int WAVES = 8;
 constexpr int QB = WAVES * 32;
@@ -868,8 +879,11 @@ namespace {
 // SPLIT: the key-split launch (AttnArgs split_*): a half workgroup runs the flash loop over its half of the keys and
 // writes O (unnormalised), the running max and the row sum instead of the output; attn_split_merge_kernel combines the
 // two halves
-template <int NW, bool SPLIT = false>
-__device__ __forceinline__ void attn_fwd_v6_body(const AttnArgs& a) {
+// SPARSE: the block loop runs the query block's list (AttnSparseArgs) instead of 0 .. nkb - 1; an empty list is a
+// segment with no keys
+template <int NW, bool SPLIT = false, bool SPARSE = false>
+__device__ __forceinline__ void attn_fwd_v6_body(const std::conditional_t<SPARSE, AttnSparseArgs, AttnArgs>& a) {
+  static_assert(!SPARSE || (NW == 8 && !SPLIT), "the block list serves the 8-wave whole-tile launches");
   constexpr int QBW = NW * 32, PPW = 16 / NW;  // query rows per workgroup, K (and V) 1-KB pieces per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int qb, h, seg, half = -1, stile = 0;
@@ -916,7 +930,15 @@ __device__ __forceinline__ void attn_fwd_v6_body(const AttnArgs& a) {
     }
     return;
   }
-  if (kv_len <= 0) {  // a segment with no keys: zeros, as SDPA (nothing to add when accumulating)
+  [[maybe_unused]] const int* bl = nullptr;  // SPARSE: this query block's list and its length
+  [[maybe_unused]] int nbl = 0;
+  if constexpr (SPARSE) {
+    const int p0 = sload(a.blk_ptr + qb);
+    nbl = sload(a.blk_ptr + qb + 1) - p0;
+    bl = a.blk_idx + p0;
+  }
+  // a segment with no keys: zeros, as SDPA (nothing to add when accumulating)
+  if (kv_len <= 0 || (SPARSE && nbl <= 0)) {
     if (!a.accumulate)
       for (int i = tid; i < QBW * (D / 8); i += NW * 64) {
         const int qi = qb * QBW + i / (D / 8);
@@ -1010,22 +1032,50 @@ __device__ __forceinline__ void attn_fwd_v6_body(const AttnArgs& a) {
   st.negm[0] = st.negm[1] = 0.f;
   st.negm4[0] = st.negm4[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  stage(0, 0);
-  if (NW == 8 && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (1 < nkb) stage(1, 1);
-  attn_v6_block<0, TILE_BYTES, true>(st, qf, ka, va, 0, kv_len, g);
-  for (int kb = 1; kb < nkb; kb += 2) {
+  if constexpr (SPARSE) {
+    // the dense loop below over list positions: kc is the block being run, kn the one staged behind it, and the entry
+    // after that is read (clamped to the list) before the barrier that precedes its staging
+    auto at = [&](int i) { return sload(bl + min(i, nbl - 1)); };
+    int kc = at(0), kn = at(1);
+    stage(kc, 0);
+    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kb + 1 < nkb) stage(kb + 1, 0);
-    attn_v6_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, va, kb, kv_len, g);
-    if (kb + 1 >= nkb) break;
+    if (1 < nbl) stage(kn, 1);
+    attn_v6_block<0, TILE_BYTES, true>(st, qf, ka, va, kc, kv_len, g);
+    for (int i = 1; i < nbl; i += 2) {
+      kc = kn;
+      kn = at(i + 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (i + 1 < nbl) stage(kn, 0);
+      attn_v6_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, va, kc, kv_len, g);
+      if (i + 1 >= nbl) break;
+      kc = kn;
+      kn = at(i + 2);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (i + 2 < nbl) stage(kn, 1);
+      attn_v6_block<0, TILE_BYTES, false>(st, qf, ka, va, kc, kv_len, g);
+    }
+  } else {
+    stage(0, 0);
+    if (NW == 8 && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kb + 2 < nkb) stage(kb + 2, 1);
-    attn_v6_block<0, TILE_BYTES, false>(st, qf, ka, va, kb + 1, kv_len, g);
+    if (1 < nkb) stage(1, 1);
+    attn_v6_block<0, TILE_BYTES, true>(st, qf, ka, va, 0, kv_len, g);
+    for (int kb = 1; kb < nkb; kb += 2) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (kb + 1 < nkb) stage(kb + 1, 0);
+      attn_v6_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, va, kb, kv_len, g);
+      if (kb + 1 >= nkb) break;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (kb + 2 < nkb) stage(kb + 2, 1);
+      attn_v6_block<0, TILE_BYTES, false>(st, qf, ka, va, kb + 1, kv_len, g);
+    }
   }
 
   if (SPLIT && half >= 0) {  // partials: O^T[d][query] of this lane's d = 16 dt + 4 g + i, the query's max and sum
@@ -1079,7 +1129,9 @@ __device__ __forceinline__ void attn_fwd_v6_body(const AttnArgs& a) {
 // element of a row readable and finite through that block: the partial last block reads the keys past kv_len,
 // masked to P = 0).  2-stage K/V ring: block kb+1's DMA issued at block kb (one block of lead, vmcnt(0) +
 // __syncthreads() per block).
-__device__ __forceinline__ void attn_fwd_vt_body(const AttnArgs& a) {
+// SPARSE: as attn_fwd_v6_body's
+template <bool SPARSE = false>
+__device__ __forceinline__ void attn_fwd_vt_body(const std::conditional_t<SPARSE, AttnSparseArgs, AttnArgs>& a) {
   constexpr int NW = 8, QBW = NW * 32, PPW = 16 / NW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nx = gridDim.x, ny = gridDim.y;
@@ -1089,7 +1141,14 @@ __device__ __forceinline__ void attn_fwd_vt_body(const AttnArgs& a) {
   const int q_row0 = sg[0], q_len = sg[1], kv_row0 = sg[2], kv_len = sg[3];
   if (qb * QBW >= q_len) return;
   const int tid = threadIdx.x, lane = tid & 63;
-  if (kv_len <= 0) {
+  [[maybe_unused]] const int* bl = nullptr;
+  [[maybe_unused]] int nbl = 0;
+  if constexpr (SPARSE) {
+    const int p0 = sload(a.blk_ptr + qb);
+    nbl = sload(a.blk_ptr + qb + 1) - p0;
+    bl = a.blk_idx + p0;
+  }
+  if (kv_len <= 0 || (SPARSE && nbl <= 0)) {
     if (!a.accumulate)
       for (int i = tid; i < QBW * (D / 8); i += NW * 64) {
         const int qi = qb * QBW + i / (D / 8);
@@ -1168,19 +1227,42 @@ __device__ __forceinline__ void attn_fwd_vt_body(const AttnArgs& a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   };
-  stage(0, 0);
-  if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-  sync();
-  if (1 < nkb) stage(1, 1);
-  attn_v6t_block<0, TILE_BYTES, true>(st, qf, ka, vb, 0, kv_len, g);
-  for (int kb = 1; kb < nkb; kb += 2) {
+  if constexpr (SPARSE) {  // the dense loop below over list positions (kc, kn, at: as in attn_fwd_v6_body)
+    auto at = [&](int i) { return sload(bl + min(i, nbl - 1)); };
+    int kc = at(0), kn = at(1);
+    stage(kc, 0);
+    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
     sync();
-    if (kb + 1 < nkb) stage(kb + 1, 0);
-    attn_v6t_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, vb, kb, kv_len, g);
-    if (kb + 1 >= nkb) break;
+    if (1 < nbl) stage(kn, 1);
+    attn_v6t_block<0, TILE_BYTES, true>(st, qf, ka, vb, kc, kv_len, g);
+    for (int i = 1; i < nbl; i += 2) {
+      kc = kn;
+      kn = at(i + 1);
+      sync();
+      if (i + 1 < nbl) stage(kn, 0);
+      attn_v6t_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, vb, kc, kv_len, g);
+      if (i + 1 >= nbl) break;
+      kc = kn;
+      kn = at(i + 2);
+      sync();
+      if (i + 2 < nbl) stage(kn, 1);
+      attn_v6t_block<0, TILE_BYTES, false>(st, qf, ka, vb, kc, kv_len, g);
+    }
+  } else {
+    stage(0, 0);
+    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
     sync();
-    if (kb + 2 < nkb) stage(kb + 2, 1);
-    attn_v6t_block<0, TILE_BYTES, false>(st, qf, ka, vb, kb + 1, kv_len, g);
+    if (1 < nkb) stage(1, 1);
+    attn_v6t_block<0, TILE_BYTES, true>(st, qf, ka, vb, 0, kv_len, g);
+    for (int kb = 1; kb < nkb; kb += 2) {
+      sync();
+      if (kb + 1 < nkb) stage(kb + 1, 0);
+      attn_v6t_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, vb, kb, kv_len, g);
+      if (kb + 1 >= nkb) break;
+      sync();
+      if (kb + 2 < nkb) stage(kb + 2, 1);
+      attn_v6t_block<0, TILE_BYTES, false>(st, qf, ka, vb, kb + 1, kv_len, g);
+    }
   }
 
 #pragma unroll
@@ -1448,6 +1530,11 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a) {
 }
 __global__ __launch_bounds__(256, 2) void attn_fwd_v6_w4_kernel(AttnArgs a) { attn_fwd_v6_body<4>(a); }
 __global__ __launch_bounds__(512) void attn_fwd_v6t_kernel(AttnArgs a) { attn_fwd_vt_body(a); }
+// the block-sparse launches of the two 8-wave bodies (sa_attn_fwd_sparse)
+__global__ __launch_bounds__(512) void attn_fwd_v6_sparse_kernel(AttnSparseArgs a) {
+  attn_fwd_v6_body<8, false, true>(a);
+}
+__global__ __launch_bounds__(512) void attn_fwd_v6t_sparse_kernel(AttnSparseArgs a) { attn_fwd_vt_body<true>(a); }
 
 }  // namespace
 
@@ -1502,6 +1589,39 @@ extern "C" int sa_attn_fwd_map(const void* q, const void* k, const void* v, void
     dim3 grid((max_q_len + QB - 1) / QB, heads, nseg);
     hipLaunchKernelGGL(attn_fwd_v6_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
   }
+  SA_LAUNCH_CHECK();
+  return SA_OK;
+}
+
+// sa_attn_fwd_map over a block list per 256-query block (include/stableavatar_hip.h): kernel 0 and 1 run the row-major
+// 8-wave body, 3 the V^T one; the 4-wave kernel 2 and the key-split launch have no sparse form
+extern "C" int sa_attn_fwd_sparse(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int nseg,
+                                  int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
+                                  int64_t v_stride, int64_t o_stride, float scale, int accumulate, int kernel,
+                                  const int32_t* o_rows, const int32_t* blk_ptr, const int32_t* blk_idx, int n_qblocks,
+                                  void* stream) {
+  if (!q || !k || !v || !o || !segs || nseg <= 0 || max_q_len <= 0 || heads <= 0) return SA_ERR_ARG;
+  if (head_dim != D) return SA_ERR_ARG;
+  if ((q_stride | k_stride | v_stride | o_stride) % 8) return SA_ERR_ARG;
+  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return SA_ERR_ARG;
+  if (kernel != 0 && kernel != 1 && kernel != 3) return SA_ERR_ARG;
+  if (kernel == 3 && (v_stride % 64 || (((uintptr_t)v) & 127))) return SA_ERR_ARG;  // V^T rows: whole 64-key blocks
+  if (!blk_ptr || !blk_idx || ((((uintptr_t)blk_ptr) | ((uintptr_t)blk_idx)) & 3)) return SA_ERR_ARG;
+  if (n_qblocks != (max_q_len + QB - 1) / QB) return SA_ERR_ARG;
+  static const bool attr = [] {
+    (void)hipFuncSetAttribute((const void*)attn_fwd_v6_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_v6t_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_BYTES);
+    return true;
+  }();
+  (void)attr;
+  AttnSparseArgs a{{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, segs,
+                    q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, accumulate, o_rows},
+                   blk_ptr, blk_idx};
+  const dim3 grid(n_qblocks, heads, nseg);
+  if (kernel == 3) hipLaunchKernelGGL(attn_fwd_v6t_sparse_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(attn_fwd_v6_sparse_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
   SA_LAUNCH_CHECK();
   return SA_OK;
 }

@@ -27,6 +27,10 @@ Flag mapping:
 * ``--fp8_o`` (no counterpart in the reference): ``transformer.enable_fp8_o()``, the output projection of the DiT
   blocks' self-attention on MXFP8 operands (DESIGN.md "fp8 self-O"); with ``--fp8_attn`` the flash kernel writes the
   projection's operand itself; changes numerics; combines with every flag above;
+* ``--attn_window_frames W`` / ``--attn_sink_frames S`` (no counterpart in the reference):
+  ``transformer.enable_sparse_attention(W, S)``, the DiT blocks' self-attention restricted to the latent frames within W
+  of the query's plus the first S, at tile granularity (DESIGN.md "Sparse self-attention"); changes the function
+  computed, quality on real checkpoints unmeasured; not with ``--fp8_attn``;
 * ``--fsdp_dit`` / ``--t5_fsdp`` / ``--t5_cpu`` / ``--offload_model``: accepted, no effect (the 3.5 GB DiT is
   replicated).
 Audio is read with scipy (16-bit / float WAV, channels averaged, polyphase resampling to 16 kHz) where the
@@ -117,6 +121,16 @@ def parse_args(argv=None):
                         "and has no counterpart in the reference. With --fp8_attn the flash kernel writes the "
                         "projection's MXFP8 operand itself; without it the bf16 output takes one more quantiser pass "
                         "(DESIGN.md, fp8 self-O).")
+    p.add_argument("--attn_window_frames", type=int, default=None, metavar="W",
+                   help="block-sparse self-attention in the DiT blocks: a query attends the latent frames within W of "
+                        "its own and the first --attn_sink_frames frames, per 256-query tile and 64-key block "
+                        "(WanTransformer3DFantasyModel.enable_sparse_attention; stableavatar_amd/sparse_attn.py is the "
+                        "definition). Computes a different function from the reference; quality on real checkpoints "
+                        "is unmeasured at any window. A window of all frames reproduces the dense output. Not with "
+                        "--fp8_attn. Off by default.")
+    p.add_argument("--attn_sink_frames", type=int, default=1, metavar="S",
+                   help="with --attn_window_frames: every query also attends the first S latent frames (default 1, a "
+                        "convention, not a measured choice)")
     p.add_argument("--sampler", type=str, default="euler", choices=("euler", "unipc"),
                    help="euler: FlowMatchEulerDiscreteScheduler, the reference pipeline's sampler (default). unipc: "
                         "FlowUniPCMultistepScheduler (wan/utils/fm_solvers_unipc.py: order 2, bh2), the multistep "
@@ -305,6 +319,10 @@ def main(argv=None):
         print("fp8 self-O: the DiT blocks' self-attention output projection runs on MXFP8 operands (numerics differ "
               "from the bf16 path)")
         transformer3d.enable_fp8_o()
+    if args.attn_window_frames is not None:
+        print(f"sparse self-attention: latent frames within {args.attn_window_frames} of the query's plus the first "
+              f"{args.attn_sink_frames} (computes a different function from the dense path)")
+        transformer3d.enable_sparse_attention(args.attn_window_frames, args.attn_sink_frames)
     if args.enable_teacache:
         coefficients = get_teacache_coefficients(root)
         if coefficients is not None:

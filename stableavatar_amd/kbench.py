@@ -8,7 +8,10 @@ fp8 q/k/v mode unfused and fused, ditfp8qkv = the whole forward off / attn+ffn /
 ofp8 = the MXFP8 flash kernel + the self-attention O-projection in bf16 and with the fp8 self-O mode unfused and fused,
 ditfp8o = the whole forward off / the three modes / the three + fp8 self-O unfused / fused;
 attnfp8split = the Ulysses N = 8 rank's self-attention launch unsplit against its key-split launch, fp8 and bf16;
-unipc = sa_unipc_step beside sa_flow_step at config 2's latent shape.
+unipc = sa_unipc_step beside sa_flow_step at config 2's latent shape;
+attnsparse = the config-2 self-attention launch on dense kernel 3, on sa_attn_fwd_sparse with every block listed and
+with frame windows of a few widths (each table's density beside its time), ditsparse = the whole forward with
+enable_sparse_attention() off and on at those windows.
 gemmfp8 and qkvfp8 also time sa_gemm_mxfp8_ks's one-tile kernel (the baseline arm) against its persistent kernel and
 against the one-tile kernel with the split K step (kstep=2) on their GEMM shapes, and ditfp8qkv has
 variants that run every MXFP8 GEMM of the forward on the persistent kernel and on the one-barrier K step."""
@@ -310,6 +313,11 @@ def main(which=("gemm", "attn")):
         print(json.dumps(res[-1]), flush=True)
     if "unipc" in which:  # the UniPC sampler step beside the Euler one at config 2's latent shape, interleaved
         res.extend(bench_unipc())
+    if "attnsparse" in which:  # the block-sparse launch against dense kernel 3 at config 2, interleaved rounds
+        res.extend(bench_sparse_attn())
+    if "ditsparse" in which:  # whole-forward A/B of enable_sparse_attention(), interleaved
+        res.append(bench_dit(sparse_ab=True))
+        print(json.dumps(res[-1]), flush=True)
     if "ditvar" in which:  # in-situ A/B of attention variants inside full DiT forwards (interleaved)
         import os
         avars = tuple(int(v) for v in os.environ.get("SA_KB_AVARS", "1").split(","))
@@ -358,6 +366,60 @@ def bench_unipc(C=16, T=21, H=64, W=64, R=3, rounds=5):
         ms = sorted(times[n])[rounds // 2]
         r.update({f"{n}_us": round(1e3 * ms, 2), f"{n}_rounds_us": [round(1e3 * t, 2) for t in times[n]],
                   f"{n}_bytes": by[n], f"{n}_gbps": round(by[n] / ms / 1e6, 1)})
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
+SPARSE_WINDOWS = (8, 4, 2, 1, 0)  # frame windows of attnsparse / ditsparse, besides the window of all frames
+
+
+def _table_stats(ptr, idx, q_len, kv_len):
+    """density and the spread of the per-tile list lengths (the launch's imbalance: a tile's time follows its list)"""
+    from . import sparse_attn
+    n = (ptr[1:] - ptr[:-1]).float()
+    return {"density": round(sparse_attn.density(ptr, idx, q_len, kv_len), 4), "list_min": int(n.min()),
+            "list_mean": round(n.mean().item(), 1), "list_max": int(n.max())}
+
+
+def bench_sparse_attn(L=21504, H=12, B=3, frames=21, rounds=5):
+    """The config-2 self-attention launch (B = 3 rows of L = 21 504 tokens = 21 latent frames of 1024, 12 heads) on the
+    V^T kernel 3, same process, interleaved rounds, median of `rounds` with every round kept: dense (sa_attn_fwd_map),
+    sa_attn_fwd_sparse with every block listed (the price of the indirection; output compared byte for byte), and with
+    the frame-window tables of SPARSE_WINDOWS (sink_frames = 1).  Per table: its density, the spread of its per-tile
+    list lengths, and ms / (density x dense ms) -- 1.0 would be time proportional to the blocks visited."""
+    from . import sparse_attn
+    dev, D = "cuda", 128
+    g = torch.Generator(device=dev).manual_seed(0)
+    qkv = torch.randn(B * L, 3 * H * D, device=dev, generator=g).bfloat16()
+    q, k = qkv[:, :H * D], qkv[:, H * D:2 * H * D]
+    vt = vt_layout(qkv[:, 2 * H * D:], 3)
+    segs = torch.tensor([[b * L, L, b * L, L] for b in range(B)], dtype=torch.int32, device=dev)
+    outs = {n: torch.empty(B * L, H * D, device=dev, dtype=torch.bfloat16) for n in ("dense", "full")}
+    tabs = {"full": sparse_attn.frame_window_table(frames, L // frames, L, L, frames)}
+    tabs.update({f"w{w}": sparse_attn.frame_window_table(frames, L // frames, L, L, w) for w in SPARSE_WINDOWS})
+    dtabs = {n: tuple(x.to(dev) for x in t) for n, t in tabs.items()}
+    o = outs["full"]
+    fns = {"dense": lambda: ops.attention(q, k, vt, outs["dense"], segs, B, L, H, kernel=ops.ATTN_VT_P32)}
+    for n in tabs:
+        fns[n] = lambda n=n: ops.attention(q, k, vt, outs.get(n, o), segs, B, L, H, kernel=ops.ATTN_VT_P32,
+                                           blocks=dtabs[n])
+    times, clocks = {n: [] for n in fns}, []
+    for _ in range(rounds):
+        for n, fn in fns.items():
+            times[n].append(_time(fn, iters=5, warmup=1))
+        clocks.append(_sclk_mhz())
+    fns["dense"](), fns["full"]()
+    torch.cuda.synchronize()
+    ms = {n: sorted(t)[rounds // 2] for n, t in times.items()}
+    fl = 4.0 * B * H * L * L * D
+    r = {"kernel": "attn_sparse_self", "L": L, "heads": H, "rows": B, "frames": frames, "sclk_mhz": clocks,
+         "full_equals_dense": bool(torch.equal(outs["full"], outs["dense"])),
+         "dense_ms": round(ms["dense"], 4), "dense_tflops": round(fl / ms["dense"] / 1e9, 1),
+         "rounds_ms": {n: [round(t, 4) for t in times[n]] for n in fns}}
+    for n, t in tabs.items():
+        st = _table_stats(*t, L, L)
+        r[n] = dict(st, ms=round(ms[n], 4), ratio_vs_dense=round(ms["dense"] / ms[n], 3),
+                    ms_over_density_x_dense=round(ms[n] / (st["density"] * ms["dense"]), 3))
     print(json.dumps(r), flush=True)
     return [r]
 
@@ -838,7 +900,7 @@ def attn_clip_inputs(layers=(0, 15, 29)):
 
 
 def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp8_ab=False, fp8_attn_ab=False,
-              fp8_qkv_ab=False, fp8_o_ab=False):
+              fp8_qkv_ab=False, fp8_o_ab=False, sparse_ab=False):
     """One full 30-layer DiT forward at config 2 (B=3 CFG, 21 latent frames at 64x64, L=21504).
     attn_variants: time the forward under each self-attention schedule, interleaved rounds.
     fp8_ab: the forward with enable_fp8_ffn() off and on (two models on the same weights), interleaved rounds,
@@ -848,7 +910,10 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
     unfused; fused; fused with the MXFP8 GEMMs on their persistent kernel; and fused with every MXFP8 GEMM on the
     one-barrier K step -- each output's rel-L2 against off, whether fused equals unfused, and persistent and the
     one-barrier step equal fused, byte for byte.  fp8_o_ab: off; the three modes (attention + FFN + q/k/v); those +
-    enable_fp8_o() unfused; fused -- every round kept, each output's rel-L2 against off, whether fused equals unfused."""
+    enable_fp8_o() unfused; fused -- every round kept, each output's rel-L2 against off, whether fused equals unfused.
+    sparse_ab: one model with enable_sparse_attention() off, on at a window of all frames (every block listed: the
+    output compared byte for byte with off) and on at SPARSE_WINDOWS -- every round kept, each table's density, each
+    output's rel-L2 against off (synthetic weights: how far the function moved, not a quality figure)."""
     from . import synthetic
     from .transformer import WanTransformer3DFantasyModel, param_shapes
     cfg = dict(model_type="i2v", dim=1536, ffn_dim=8960, freq_dim=256, text_dim=4096, in_dim=36, out_dim=16,
@@ -988,6 +1053,29 @@ def bench_dit(iters=3, attn_variants=None, env_variants=None, fwd_only=False, fp
                 r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
         for k in ("four_unfused", "four_fused"):
             r[f"ratio_{k}_vs_three"] = round(r["three_ms"] / r[f"{k}_ms"], 4)
+        return r
+    if sparse_ab:
+        from . import sparse_attn
+        variants = {"off": None, "full": 21, **{f"w{w}": w for w in SPARSE_WINDOWS}}
+        times, clocks, outs = {k: [] for k in variants}, [], {}
+        with torch.no_grad():
+            for _ in range(3):
+                for k, w in variants.items():
+                    m.enable_sparse_attention(w or 0, enabled=w is not None)
+                    times[k].append(_time(fwd, iters=2, warmup=1))
+                    outs[k] = fwd().float()
+                clocks.append(_sclk_mhz())
+        m.enable_sparse_attention(0, enabled=False)
+        r = {"kernel": "dit_forward_sparse_ab", "tflop": round(fl / 1e12, 1), "sclk_mhz": clocks,
+             "full_equals_off": bool(torch.equal(outs["full"], outs["off"])),
+             "rounds_ms": {k: [round(v, 2) for v in times[k]] for k in variants}}
+        for k, w in variants.items():
+            r[f"{k}_ms"] = round(sorted(times[k])[1], 2)
+            if w is not None:
+                r[f"{k}_density"] = _table_stats(*sparse_attn.frame_window_table(21, 1024, 21504, 21504, w), 21504,
+                                                 21504)["density"]
+                r[f"rel_l2_{k}_vs_off"] = round(((outs[k] - outs["off"]).norm() / outs["off"].norm()).item(), 5)
+                r[f"ratio_{k}"] = round(r["off_ms"] / r[f"{k}_ms"], 4)
         return r
     if env_variants:  # "K=V" settings of one environment switch read per call by the library, interleaved
         import os

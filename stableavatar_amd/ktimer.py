@@ -32,7 +32,7 @@ def classify(name: str, args) -> str:
         if epi == 0 and m >= 4096:  # token-row GEMMs (the context / vocal K|V ones have a few thousand rows)
             return {3 * k: "gemm_bf16_qkv", 2 * k: "gemm_bf16_qk", k: "gemm_bf16_cross_q"}.get(n, "gemm_other")
         return "gemm_other"
-    if name in ("sa_attn_fwd_map", "sa_attn_fwd_ex", "sa_attn_fwd"):
+    if name in ("sa_attn_fwd_map", "sa_attn_fwd_ex", "sa_attn_fwd", "sa_attn_fwd_sparse"):
         return "self_attention"
     if name == "sa_attn_cross3":
         return "cross_attention"

@@ -134,11 +134,17 @@ def attn_tail_split(n_tiles_before, n_tiles, device):
 
 
 def attention(q, k, v, out, segs, nseg, max_q_len, heads, head_dim=128, scale=None, accumulate=False,
-              kernel=ATTN_AUTO, o_rows=None, split_tiles=0):
+              kernel=ATTN_AUTO, o_rows=None, split_tiles=0, blocks=None):
     """Flash attention over row-segment table `segs` (int32 [nseg,4] on device); kernel = per-call
     schedule selection (sa_attn_fwd_ex; 0 = auto); o_rows = int32 device map query row -> output row of
     `out` (sa_attn_fwd_map); split_tiles > 0: the last split_tiles tiles as two key halves + a merge
-    (sa_attn_fwd_split, 8-wave kernel)."""
+    (sa_attn_fwd_split, 8-wave kernel); blocks = (blk_ptr, blk_idx), device int32 tables of sparse_attn: each
+    256-query block attends only its listed 64-key blocks (sa_attn_fwd_sparse; kernel 0, 1 or 3, no key split)."""
+    if blocks is not None:
+        if split_tiles:
+            raise ValueError("attention: a block list has no key-split launch (blocks with split_tiles)")
+        if kernel not in (ATTN_AUTO, 1, ATTN_VT_P32):
+            raise ValueError(f"attention: a block list runs kernel 0, 1 or 3, not {kernel}")
     for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out")):
         _check(t, torch.bfloat16, f"attention.{n}")
         assert t.stride(-1) == 1
@@ -147,6 +153,15 @@ def attention(q, k, v, out, segs, nseg, max_q_len, heads, head_dim=128, scale=No
         assert o_rows.dtype == torch.int32 and o_rows.is_cuda and o_rows.is_contiguous()
     if scale is None:
         scale = head_dim ** -0.5
+    if blocks is not None:
+        blk_ptr, blk_idx = blocks
+        for t in (blk_ptr, blk_idx):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+        call("sa_attn_fwd_sparse", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), segs.data_ptr(), nseg,
+             max_q_len, heads, head_dim, q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale),
+             int(accumulate), kernel, _p(o_rows), blk_ptr.data_ptr(), blk_idx.data_ptr(), blk_ptr.numel() - 1,
+             _stream())
+        return out
     if split_tiles:
         work = torch.empty(split_tiles * 2 * 256 * (head_dim + 2), device=q.device, dtype=torch.float32)
         call("sa_attn_fwd_split", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), segs.data_ptr(), nseg,

@@ -24,7 +24,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from . import ops, sp
+from . import ops, sp, sparse_attn
 
 
 def rope_params(max_seq_len: int, dim: int, theta: float = 10000.0) -> torch.Tensor:
@@ -194,6 +194,13 @@ class _Seg:
             self._vt.pop(id(t), None)
         return t
 
+    def blocks(self, key, build, device):
+        """Device (blk_ptr, blk_idx) of a block-sparse table, built on the host by build() once per key"""
+        t = self._c.get(key)
+        if t is None or t[0].device != device:
+            t = self._c[key] = tuple(x.to(device) for x in build())
+        return t
+
     def vt_layout(self, table):
         """(vcol0, Rv, max kv_len) of a table this cache handed out: each segment's first V^T column (host-computed,
         multiples of 128) for ops.attention_mxfp8"""
@@ -268,6 +275,7 @@ class WanTransformer3DFantasyModel(nn.Module):
         self.attn_kernel = 0  # self-attention schedule (sa_attn_fwd_ex; 0 = auto), for in-situ A/B
         self._fp8_ffn = False  # enable_fp8_ffn(): the blocks' FFN GEMMs on MXFP8 operands
         self._fp8_attn = False  # enable_fp8_attention(): the blocks' self-attention on MXFP8 operands
+        self._sparse = None  # enable_sparse_attention(): (window_frames, sink_frames) of the frame-window block lists
         self._fp8_qkv = False  # enable_fp8_qkv(): the blocks' self-attention q/k/v Linears on MXFP8 operands
         # with _fp8_qkv and _fp8_attn both on, the single-GPU sites write the attention operands where their values are
         # made (_self_attention_rows); False: the mode's GEMM, then _self_attn -- the same output bytes (for the A/B)
@@ -392,6 +400,8 @@ class WanTransformer3DFantasyModel(nn.Module):
         enabled = bool(enabled)
         if enabled and self.d != 128:
             raise ValueError(f"enable_fp8_attention: head_dim {self.d} != 128")
+        if enabled and self._sparse is not None:
+            raise NotImplementedError("enable_fp8_attention: the MXFP8 flash kernel has no block-sparse form")
         if enabled != self._fp8_attn:
             self._fp8_attn = enabled
             self._ws = {}
@@ -436,6 +446,30 @@ class WanTransformer3DFantasyModel(nn.Module):
             self._packed = None
             self._ws = {}
 
+    def enable_sparse_attention(self, window_frames, sink_frames=1, enabled=True):
+        """MI355X addition (no counterpart in the reference; changes the function computed): the self-attention of
+        every DiT block (1B:383-413) attends, per 256-query tile, only the 64-key blocks of the frame-window pattern
+        (stableavatar_amd/sparse_attn.py is the definition: latent frames within window_frames of the query's, plus
+        the first sink_frames frames, at tile granularity) through sa_attn_fwd_sparse on the bf16 flash kernels.  The
+        tables depend on the grid and the sequence length alone and are cached with the segment tables; the same table
+        serves every CFG row, head and layer, and under sequence parallelism every rank (each attends the whole
+        sequence for its heads; no launch is key-split while the mode is on).  Cross-attention and the vocal projector
+        are untouched.  A window that covers every frame lists every block and reproduces the dense output byte for
+        byte.  sink_frames = 1 is a convention, not a measured choice, and quality on real checkpoints is unmeasured at
+        any window.  Not combined with enable_fp8_attention() (NotImplementedError).  Off, the calls made are the
+        dense path's."""
+        if not enabled:
+            self._sparse = None
+            return
+        if self._fp8_attn:
+            raise NotImplementedError("enable_sparse_attention: the MXFP8 flash kernel has no block-sparse form")
+        if self.d != 128:
+            raise ValueError(f"enable_sparse_attention: head_dim {self.d} != 128")
+        window_frames, sink_frames = int(window_frames), int(sink_frames)
+        if window_frames < 0 or sink_frames < 0:
+            raise ValueError("enable_sparse_attention: window_frames and sink_frames must be >= 0")
+        self._sparse = (window_frames, sink_frames)
+
     def _self_attn(self, f, q, k, v, out, segs, kernel=0, split_tiles=0):
         """One self-attention launch of a DiT block over the segment table `segs` (f: the forward's state, whose Lq,
         hg and omap are the launch's query rows per segment, heads and output row map): ops.attention, or with
@@ -447,6 +481,9 @@ class WanTransformer3DFantasyModel(nn.Module):
         on first use."""
         nseg = segs.shape[0]
         if not self._fp8_attn:
+            if f.blocks is not None:
+                return ops.attention(q, k, v, out, segs, nseg, f.Lq, f.hg, kernel=kernel, o_rows=f.omap,
+                                     split_tiles=split_tiles, blocks=f.blocks)
             return ops.attention(q, k, v, out, segs, nseg, f.Lq, f.hg, kernel=kernel, o_rows=f.omap,
                                  split_tiles=split_tiles)
         vcol0, Rv, max_kv = self._segs.vt_layout(segs)
@@ -849,7 +886,12 @@ class WanTransformer3DFantasyModel(nn.Module):
             ops.linear(mod, L.w_v, L.b_v, ops.EPI_BF16_TP32, out=ws.vt)
             ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **f.rope_kw)
             with self._span(rows=nb, batch=f.B):
-                ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_, kernel=ops.ATTN_VT_P32)
+                if f.blocks is not None:
+                    ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_,
+                                  kernel=ops.ATTN_VT_P32, blocks=f.blocks)
+                else:
+                    ops.attention(qkv[:, :dim], qkv[:, dim:2 * dim], ws.vt, att, segs, nb, Lp, H_,
+                                  kernel=ops.ATTN_VT_P32)
         else:
             self._qkv(f, L, R, e, normed=True)
             ops.qk_rmsnorm_rope(qkv, 0, dim, L.nq, L.nk, dim, self.eps, **f.rope_kw)
@@ -930,7 +972,8 @@ class WanTransformer3DFantasyModel(nn.Module):
                 self._sp_o_proj(f, L, em, b, back[b])
             return
         # one batched attention once all have arrived, its tiles past the last full round over the CUs as key halves
-        split = ops.attn_tail_split(0, f.B * f.hg * -(-f.Lq // 256), f.dev) if self.attn_kernel == 0 else 0
+        split = (ops.attn_tail_split(0, f.B * f.hg * -(-f.Lq // 256), f.dev)
+                 if self.attn_kernel == 0 and f.blocks is None else 0)
         self._sp_o_proj(f, L, em, None, self._sp_attend(f, None, pend, self.attn_kernel, split))
 
     def _sp_block_streams(self, f, L, em, sa):
@@ -947,8 +990,8 @@ class WanTransformer3DFantasyModel(nn.Module):
         # the fp8 attention mode: there the three concurrent launches measured 3 % slower with the last row's tail
         # split than without (profiles/r10/fp8_attn_split.jsonl), so its key split serves the batched launch alone
         n_row = f.hg * -(-f.Lq // 256)
-        splits = [ops.attn_tail_split(b * n_row, n_row, f.dev) if self.attn_kernel == 0 and not self._fp8_attn
-                  else 0 for b in range(f.B)]
+        splits = [ops.attn_tail_split(b * n_row, n_row, f.dev)
+                  if self.attn_kernel == 0 and not self._fp8_attn and f.blocks is None else 0 for b in range(f.B)]
         akern = 1 if any(splits) else self.attn_kernel
         pend, back = [], []
         for b, st in enumerate(f.streams if sa else []):  # self-attention inputs (1B:675-676) and the Q/K/V exchange
@@ -1156,6 +1199,14 @@ class WanTransformer3DFantasyModel(nn.Module):
                 t.img = get(("rimg", b, Lc, ni), [[0, Lc, b * ni, ni]], dev)
                 t.voc = get(("rvoc", b, Lc, tuple(map(tuple, vl))), vl, dev)
                 t.voc_n, t.voc_q = len(vl), max(s_[1] for s_ in vl)
+        if self._sparse is not None:
+            # the block lists of every self-attention launch of this forward: f.Lq queries -- under sequence parallelism
+            # this rank's query part, tokens part * Lq onwards -- against the S keys of a row
+            (Fw, Hg, Wg), (win, sink) = f.grid, self._sparse
+            q0 = f.Lq * sp.make_plan(f.NS, rank, self.num_heads).part if self._sp_enabled else 0
+            f.blocks = self._segs.blocks(
+                ("blocks", Fw, Hg * Wg, Lq, S, win, sink, q0),
+                lambda: sparse_attn.frame_window_table(Fw, Hg * Wg, Lq, S, win, sink, q_offset=q0), dev)
         f.use_cross3 = (ni > 0 and f.G % 256 == 0 and (rank * Lc) % 256 == 0 and (rank + 1) * Lc <= S
                         and os.environ.get("SA_CROSS3", "1") != "0")
         f.use_vt = not self._sp_enabled and not self._fp8_attn and not self._fp8_qkv and self._vt_attention(Lp, dev)
@@ -1226,7 +1277,7 @@ class WanTransformer3DFantasyModel(nn.Module):
             fhw=(Fw, Hh, Ww), grid=grid,
             rope_kw=dict(rope=pk.rope, rows_per_batch=Lc, tok_offset=rank * Lc, grid=grid, head_dim=d,
                          n_frame_pairs=d // 2 - 2 * (d // 6), n_height_pairs=d // 6),
-            ex=None, omap=None, schedule=None, Lq=Lp, hg=self.num_heads)
+            ex=None, omap=None, schedule=None, Lq=Lp, hg=self.num_heads, blocks=None)
 
         xfull = self._patch_embed(f, lat, y, frame_offset, broadcast)
         e, e0, emod, hmod = self._time_modulation(f, t)
