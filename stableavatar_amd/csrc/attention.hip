@@ -13,11 +13,20 @@
 // KV blocks of 64 keys staged by global_load_lds into a 2-deep LDS ring (XOR-swizzled 256-B rows).
 // Swapped product S^T = K·Q^T puts one query per lane, so the online softmax is lane-local; P^T is
 // fed back as the B operand straight from the accumulator and V^T comes from ds_read_b64_tr_b16,
-// giving O^T with the query on the lane (rescale is per lane).  Self-attention runs the
-// mfma_f32_16x16x32_bf16 block body (attn_v6_block), shared by the self-attention kernels and the fused
-// cross-attention.
+// giving O^T with the query on the lane (rescale is per lane).
+//
+// Layout of this file: the small-query kernels; the pieces of a 64-key block on mfma_f32_16x16x32_bf16 (v6_*), the
+// two V layouts (VRows: V rows beside K, VTrans: V^T from the QKV GEMM's epilogue) and the one block over them,
+// attn_v6_block; the pieces of a kernel body (attn_grid_tile, attn_zero_rows, attn_load_q, attn_row_rsrc /
+// attn_row_load, attn_k_bases, attn_pair16, attn_store_o) and the one 2-stage ring, attn_ring2 (a plain counter, or a
+// block list for the sparse launches).  Every self-attention kernel -- 8 waves, 4 waves, the key split, V^T, and the
+// block-sparse forms of the 8-wave ones -- is attn_fwd_body<layout, waves, SPLIT, SPARSE>; the fused cross-attention
+// (attn_cross3_body) keeps its own staging (three sources through per-block descriptors) and its NST-stage ring, and
+// takes the rest from the same pieces.  What each kernel kept of its own, and the records that say the fold left
+// bytes, loops and speed alone: DESIGN.md, "Self-attention, the fold".
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "common.h"
@@ -57,31 +66,14 @@ constexpr int TILE_BYTES = KVB * D * 2;      // 16 KB
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // K + V
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 64 KB
 
-// 16-byte chunk swizzle for 256-B rows: conflict-free for both row (ds_read_b128) and
-// transposed (ds_read_b64_tr_b16) reads (cdna_hip_programming.md T10 form (b))
-__device__ __forceinline__ int gsw(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
 constexpr float RESCALE_THR = 8.0f;  // log2 units: P <= 2^8 between rescales (fused cross-attention)
 // self-attention blocks (v6_softmax_p): the running max sits RESCALE_BIAS above the rows' maxima after each move, and
 // the next move comes when a score passes its row's maximum by RESCALE_BIAS + 1 = RESCALE_THR
 constexpr float RESCALE_BIAS = RESCALE_THR - 1.0f;
 
-// non-canonicalising f32 max (MFMA outputs are never signalling NaNs): fmaxf makes hipcc insert a
-// v_max_f32 x, x canonicalisation per operand (MI355X_MICROARCH.md, App. B attention pitfalls).  The
-// IEEE-2019 maximum lowers to gfx950's v_maximum3_f32 with no canonicalisation, and, unlike an inline-asm
-// v_max3_f32, needs no conservative s_nop after each link of a dependent chain (hipcc pads every VGPR an
-// asm statement defines before the next VALU reads it: 16+ s_nop per block on the rescale test)
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
-}
+// vmax3's two-operand form (common.h)
 __device__ __forceinline__ float vmax2(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-// LDS reads issued from inline asm at base+immediate addresses and retired by counted lgkmcnt waits
-// (cdna_hip_programming.md §5.7 item 1 form (ii)), so hipcc neither serialises each fragment behind its own
-// wait nor drains the next block's LDS-DMA (vmcnt(0)) before them
-template <int OFF>
-__device__ __forceinline__ void ds_b128(u32x4& d, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
-}
+// the transposed LDS read, issued and retired as ds_b128 (common.h)
 template <int OFF>
 __device__ __forceinline__ void ds_tr64(u32x2& d, uint32_t addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
@@ -95,7 +87,7 @@ __device__ __forceinline__ void wait_v(u32x2* f) {
 // The fused cross-attention keeps K and V of a block in separate 3-stage regions (K stage b at b * 16 KB,
 // V stage b at 48 KB + b * 16 KB; the V read bases include the 48 KB) so a block's DMA is issued two blocks
 // ahead
-constexpr int X3_VBASE = 3 * TILE_BYTES, X3_LDS = 6 * TILE_BYTES;  // 96 KB
+constexpr int X3_LDS = 6 * TILE_BYTES;  // 96 KB
 
 // ---- fused cross-attention of WanI2VTalkingCrossAttention (1B:556-603): per query block, the text
 // (1B:564-570), image (1B:556-562) and per-frame vocal (1B:575-586) attentions run back to back over
@@ -445,7 +437,8 @@ __device__ __forceinline__ void v6_read_v(u32x2* f, const uint32_t* va) {
   ds_tr64<base>(f[4], va[DT0 + 2]); ds_tr64<base + 4096>(f[5], va[DT0 + 2]);
   ds_tr64<base>(f[6], va[DT0 + 3]); ds_tr64<base + 4096>(f[7], va[DT0 + 3]);
 }
-__device__ __forceinline__ void v6_mma_k(f32x4 (&S)[4][2], int kt, const u32x4* f, const bf16x8 (&qf)[2][4]) {
+template <int NKT>
+__device__ __forceinline__ void v6_mma_k(f32x4 (&S)[NKT][2], int kt, const u32x4* f, const bf16x8 (&qf)[2][4]) {
 #pragma unroll
   for (int dc = 0; dc < 4; ++dc) {
     S[kt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v6_as_bf8(f[dc]), qf[0][dc], S[kt][0], 0, 0, 0);
@@ -470,6 +463,15 @@ struct V6State {
   f32x4 L[2];     // row sums of the bf16 P (every element equal), from a ones x P^T MFMA
   float negm[2];  // -m per query tile (this lane's query)
   f32x4 negm4[2];  // the same as the QK^T chains' initial accumulator (refreshed only on a rescale)
+  __device__ __forceinline__ void reset() {
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) O[dt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    L[0] = L[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    negm[0] = negm[1] = 0.f;
+    negm4[0] = negm4[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
 };
 
 // max over 16 values of one query's S^T column slice, then over the 4 lane groups (permlane32 / 16 swaps)
@@ -556,7 +558,7 @@ __device__ __forceinline__ void v6_pack_exp(const f32x4 (&S)[4][2], bf16x8 (&pb)
       }
 }
 
-// The online-softmax step of one 64-key block (attn_v6_block, attn_v6t_block): P into pb, the running max moved
+// The online-softmax step of one 64-key block (attn_v6_block): P into pb, the running max moved
 // first where needed.  The running max is kept RESCALE_BIAS log2 units above the rows' maxima (P <= 2^-7 right after
 // a move), and the test runs on the bf16 P: some P >= 2 -- a score 8 above its row's maximum -- iff bit 14 of some
 // packed P is set (P >= 0: biased exponent >= 128), so the OR of the 16 P dwords (8 v_or3) decides, where a max tree
@@ -607,91 +609,12 @@ __device__ __forceinline__ void v6_softmax_p(V6State& st, f32x4 (&S)[4][2], bf16
   }
 }
 
-// one 64-key block whose K / V stages sit at KOFF / VOFF from the read bases (self-attention: K and V of a
-// stage adjacent in a 2-stage ring; the fused cross-attention: separate 3-stage K and V regions).  The first
-// block of a softmax sets the running max: FIRST_CT at compile time (self-attention), first_rt per source
-// (cross-attention)
-template <int KOFF, int VOFF, bool FIRST_CT, bool PTEST = true>
-__device__ __forceinline__ void attn_v6_block(V6State& st, const bf16x8 (&qf)[2][4], const uint32_t* ka,
-                                              const uint32_t* va, int kb, int kv_len, int g,
-                                              bool first_rt = false) {
-  f32x4 S[4][2];
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-      S[kt][qt] = st.negm4[qt];
-  // S'^T = c K Q^T - m, K fragments two key tiles ahead
-  u32x4 k0[4], k1[4];
-  v6_read_k<KOFF, 0>(k0, ka);
-  v6_read_k<KOFF, 1>(k1, ka);
-  wait_k4<4>(k0);
-  v6_mma_k(S, 0, k0, qf);
-  v6_read_k<KOFF, 2>(k0, ka);
-  wait_k4<4>(k1);
-  v6_mma_k(S, 1, k1, qf);
-  v6_read_k<KOFF, 3>(k1, ka);
-  wait_k4<4>(k0);
-  v6_mma_k(S, 2, k0, qf);
-  wait_k4<0>(k1);
-  v6_mma_k(S, 3, k1, qf);
-  // first V^T fragments under the softmax
-  u32x2 v0[8], v1[8];
-  v6_read_v<VOFF, 0, 0>(v0, va);
-  v6_read_v<VOFF, 0, 4>(v1, va);
-
-  if (kb * KVB + KVB > kv_len) {
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (kb * KVB + kt * 16 + 4 * g + i >= kv_len) { S[kt][0][i] = -INFINITY; S[kt][1][i] = -INFINITY; }
-  }
-  // PTEST: the self-attention kernels' step (P-side rescale test, P for the whole block); else the fused
-  // cross-attention's (v6_softmax_s: P formed per key chunk below)
-  bf16x8 pb[2][2];
-  if constexpr (PTEST) v6_softmax_p<FIRST_CT>(st, S, pb, first_rt);
-  else v6_softmax_s(st, S, FIRST_CT || first_rt);
-  // O^T += V^T P^T, key chunk c = tiles (2c, 2c+1)
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    if constexpr (!PTEST)
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          pb[c][qt][j] = f2bf(S[2 * c][qt][j]);
-          pb[c][qt][4 + j] = f2bf(S[2 * c + 1][qt][j]);
-        }
-    {
-      bf16x8 ones;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.0f;
-      st.L[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[c][0], st.L[0], 0, 0, 0);
-      st.L[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[c][1], st.L[1], 0, 0, 0);
-    }
-    if (c == 0) {
-      wait_v<8>(v0);
-      v6_mma_v(st.O, 0, v0, pb[c]);
-      v6_read_v<VOFF, 1, 0>(v0, va);
-      wait_v<8>(v1);
-      v6_mma_v(st.O, 4, v1, pb[c]);
-      v6_read_v<VOFF, 1, 4>(v1, va);
-    } else {
-      wait_v<8>(v0);
-      v6_mma_v(st.O, 0, v0, pb[c]);
-      wait_v<0>(v1);
-      v6_mma_v(st.O, 4, v1, pb[c]);
-    }
-  }
-}
-
-// ---- V^T forms of the block (V read as V^T from a d-major producer layout, [H*128][Rv] bf16: row h*128 + d holds
+// ---- V^T form of the PV operand (V read as V^T from a d-major producer layout, [H*128][Rv] bf16: row h*128 + d holds
 // d of head h for every key row), so each PV operand is ds_read_b128 instead of two ds_read_b64_tr_b16.
-// v6t: the v6 block with V^T staged 128 d-rows x 64 keys (128 B per d-row, 16-B chunk c of row d at position
-//   c ^ (d & 7)); the producer stores the keys of each 32-key chunk in P's permuted order (position 8g + j <-> key
-//   4g + j, j < 4; 16 + 4g + j - 4, j >= 4), so a lane's 16x16x32 PV operand is one b128 read.  (Measured and
-//   removed, records under profiles/r05/: the PV product on 32x32x16 MFMAs, a two-wave ping-pong, a 3-stage ring.)
+// V^T is staged 128 d-rows x 64 keys (128 B per d-row, 16-B chunk c of row d at position c ^ (d & 7)); the producer
+//   stores the keys of each 32-key chunk in P's permuted order (position 8g + j <-> key 4g + j, j < 4;
+//   16 + 4g + j - 4, j >= 4), so a lane's 16x16x32 PV operand is one b128 read.  (Measured and removed, records under
+//   profiles/r05/: the PV product on 32x32x16 MFMAs, a two-wave ping-pong, a 3-stage ring.)
 template <int VOFF, int C, int T0>
 __device__ __forceinline__ void v6t_read_v(u32x4* f, const uint32_t* vb) {
   ds_b128<VOFF + (T0 + 0) * 2048>(f[0], vb[C]);
@@ -708,6 +631,99 @@ __device__ __forceinline__ void v6t_mma_v(f32x4 (&O)[8][2], int dt0, const u32x4
   }
 }
 
+// descriptors of one head's rows of a row-major K (or V) of a segment: `all` over rows 0 .. len - 1 (a block in
+// soffset), and a partial last block's own (base = its first row, soffset 0) whose range ends at the segment's last
+// row, so its rows past len read as zeros (masked in S, and 0 x 0 in PV) instead of whatever follows.  The range check
+// takes voffset + soffset + the instruction offset against the records (a V^T form reading per-source chunks, measured
+// and removed in round 6, read zeros past a records value that left soffset out)
+struct RowRsrc {
+  __amdgpu_buffer_rsrc_t all, tail;
+};
+__device__ __forceinline__ RowRsrc attn_row_rsrc(const bf16* p, long stride, int row0, int len, int h) {
+  const long tail0 = (long)((len + KVB - 1) / KVB - 1) * KVB;  // first row of the last block
+  return {__builtin_amdgcn_make_buffer_rsrc((void*)(p + (long)row0 * stride + h * D), (short)0,
+                                            (int)(((long)len - 1) * stride * 2 + 256), 0x00020000),
+          __builtin_amdgcn_make_buffer_rsrc((void*)(p + (row0 + tail0) * stride + h * D), (short)0,
+                                            (int)((len - tail0 - 1) * stride * 2 + 256), 0x00020000)};
+}
+// one 1-KB piece (4 rows) of block kb into LDS at dst: by buffer_load...lds from the SGPR descriptor, a per-lane 32-bit
+// offset and the block in soffset -- no 64-bit address VALU.  tail: kb is the partial last block (wave-uniform)
+__device__ __forceinline__ void attn_row_load(const RowRsrc& r, bool tail, int kb, int stride, uint32_t dst, int off) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(tail ? r.tail : r.all, LDS_PTR((uintptr_t)dst), 16, off,
+                                           tail ? 0 : kb * KVB * stride * 2, 0, 0);
+}
+
+// ---- V layouts: how a block's V gets into its 16-KB LDS tile (Src, off, load: piece = 1 KB, 16 per block), and from
+// there into the PV MFMAs' A operand (bases, read, wait, mma: a fragment group = the operands of 4 d tiles, NF
+// registers of type Frag).  Everything else of a block and of a kernel body is written once over them.
+// VRows: V row-major beside K; LDS rows chunk ^ 2(row & 7); two ds_read_b64_tr_b16 per operand from bases va[d tile]
+struct VRows {
+  using Frag = u32x2;
+  using Src = RowRsrc;
+  static constexpr int NF = 8, NBASE = 8;
+  static __device__ __forceinline__ Src src(const bf16* v, long vs, int row0, int len, int h) {
+    return attn_row_rsrc(v, vs, row0, len, h);
+  }
+  static __device__ __forceinline__ int off(int piece, int lane, int vs) {
+    const int srow = piece * 4 + (lane >> 4);
+    return srow * vs * 2 + (((lane & 15) ^ ((srow & 7) << 1)) << 4);
+  }
+  static __device__ __forceinline__ void load(const Src& r, bool tail, int kb, int vs, uint32_t dst, int off) {
+    attn_row_load(r, tail, kb, vs, dst, off);
+  }
+  // lds_v: the V tile of stage 0; the rest are +immediate
+  static __device__ __forceinline__ void bases(uint32_t (&va)[NBASE], uint32_t lds_v, int g, int r16) {
+    const int q = r16 >> 2, p = r16 & 3;
+    const int row = 4 * g + q;  // + 32 c (+16): same swizzle
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+      const int ch = 2 * dt + (p >> 1);
+      va[dt] = lds_v + row * 256 + ((ch ^ ((row & 7) << 1)) << 4) + 8 * (p & 1);
+    }
+  }
+  template <int VOFF, int C, int T0>
+  static __device__ __forceinline__ void read(Frag* f, const uint32_t* va) { v6_read_v<VOFF, C, T0>(f, va); }
+  template <int N>
+  static __device__ __forceinline__ void wait(Frag* f) { wait_v<N>(f); }
+  static __device__ __forceinline__ void mma(f32x4 (&O)[8][2], int dt0, const Frag* f, const bf16x8 (&pb)[2]) {
+    v6_mma_v(O, dt0, f, pb);
+  }
+};
+// VTrans: V^T [heads * 128][vs] (v6t_read_v above); one ds_read_b128 per operand from bases vb[key chunk].  vs >= the
+// columns any segment's last 64-key block reaches, i.e. kv_row0 + ceil64(kv_len); segments start on 32-key boundaries;
+// every element of a row readable and finite through that block: the partial last block reads the keys past kv_len,
+// masked to P = 0
+struct VTrans {
+  using Frag = u32x4;
+  using Src = __amdgpu_buffer_rsrc_t;
+  static constexpr int NF = 4, NBASE = 2;
+  // the head's 128 d-rows from key row0, each through the segment's last block
+  static __device__ __forceinline__ Src src(const bf16* v, long vs, int row0, int len, int h) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(v + (long)h * D * vs + row0), (short)0,
+                                             (int)(((long)(D - 1) * vs + (long)((len + KVB - 1) / KVB) * KVB) * 2),
+                                             0x00020000);
+  }
+  static __device__ __forceinline__ int off(int piece, int lane, int vs) {
+    const int d = piece * 8 + (lane >> 3);  // a 1-KB piece = 8 d-rows x 128 B
+    return d * vs * 2 + (((lane & 7) ^ (d & 7)) << 4);
+  }
+  static __device__ __forceinline__ void load(const Src& r, bool, int kb, int, uint32_t dst, int off) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, LDS_PTR((uintptr_t)dst), 16, off, kb * KVB * 2, 0, 0);
+  }
+  static __device__ __forceinline__ void bases(uint32_t (&vb)[NBASE], uint32_t lds_v, int g, int r16) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) vb[c] = lds_v + r16 * 128 + (((4 * c + g) ^ (r16 & 7)) << 4);
+  }
+  template <int VOFF, int C, int T0>
+  static __device__ __forceinline__ void read(Frag* f, const uint32_t* vb) { v6t_read_v<VOFF, C, T0>(f, vb); }
+  template <int N>
+  static __device__ __forceinline__ void wait(Frag* f) { wait_k4<N>(f); }
+  static __device__ __forceinline__ void mma(f32x4 (&O)[8][2], int dt0, const Frag* f, const bf16x8 (&pb)[2]) {
+    v6t_mma_v(O, dt0, f, pb);
+  }
+};
+
+// S'^T = c K Q^T - m of a block, K fragments two key tiles ahead
 template <int KOFF>
 __device__ __forceinline__ void v6_qk(f32x4 (&S)[4][2], const f32x4 (&negm4)[2], const bf16x8 (&qf)[2][4],
                                       const uint32_t* ka) {
@@ -740,38 +756,56 @@ __device__ __forceinline__ void v6_tail_mask(f32x4 (&S)[4][2], int kb, int kv_le
   }
 }
 
-template <int KOFF, int VOFF, bool FIRST>
-__device__ __forceinline__ void attn_v6t_block(V6State& st, const bf16x8 (&qf)[2][4], const uint32_t* ka,
-                                               const uint32_t* vb, int kb, int kv_len, int g) {
+// row sums of a key chunk's bf16 P: a ones x P^T MFMA per query tile
+__device__ __forceinline__ void v6_rowsum(V6State& st, const bf16x8 (&pb)[2]) {
+  bf16x8 ones;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.0f;
+  st.L[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[0], st.L[0], 0, 0, 0);
+  st.L[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[1], st.L[1], 0, 0, 0);
+}
+
+// one 64-key block whose K / V stages sit at KOFF / VOFF from the read bases (self-attention: K and V of a
+// stage adjacent in a 2-stage ring; the fused cross-attention: separate NST-stage K and V regions), V in layout VL.
+// The first block of a softmax sets the running max: FIRST_CT at compile time (self-attention), first_rt per source
+// (cross-attention).  PTEST: the self-attention kernels' softmax step (P-side rescale test, P for the whole block);
+// else the fused cross-attention's (v6_softmax_s, P formed per key chunk)
+template <class VL, int KOFF, int VOFF, bool FIRST_CT, bool PTEST = true>
+__device__ __forceinline__ void attn_v6_block(V6State& st, const bf16x8 (&qf)[2][4], const uint32_t* ka,
+                                              const uint32_t* va, int kb, int kv_len, int g,
+                                              bool first_rt = false) {
   f32x4 S[4][2];
   v6_qk<KOFF>(S, st.negm4, qf, ka);
-  u32x4 v0[4], v1[4];
-  v6t_read_v<VOFF, 0, 0>(v0, vb);
-  v6t_read_v<VOFF, 0, 4>(v1, vb);
+  // first V fragments under the softmax
+  typename VL::Frag v0[VL::NF], v1[VL::NF];
+  VL::template read<VOFF, 0, 0>(v0, va);
+  VL::template read<VOFF, 0, 4>(v1, va);
   v6_tail_mask(S, kb, kv_len, g);
   bf16x8 pb[2][2];
-  v6_softmax_p<FIRST>(st, S, pb, false);
+  if constexpr (PTEST) v6_softmax_p<FIRST_CT>(st, S, pb, first_rt);
+  else v6_softmax_s(st, S, FIRST_CT || first_rt);
+  // O^T += V^T P^T, key chunk c = tiles (2c, 2c+1); chunk 1's fragments are read as chunk 0's are consumed
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    {
-      bf16x8 ones;
+    if constexpr (!PTEST)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.0f;
-      st.L[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[c][0], st.L[0], 0, 0, 0);
-      st.L[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[c][1], st.L[1], 0, 0, 0);
-    }
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          pb[c][qt][j] = f2bf(S[2 * c][qt][j]);
+          pb[c][qt][4 + j] = f2bf(S[2 * c + 1][qt][j]);
+        }
+    v6_rowsum(st, pb[c]);
+    VL::template wait<VL::NF>(v0);
+    VL::mma(st.O, 0, v0, pb[c]);
     if (c == 0) {
-      wait_k4<4>(v0);
-      v6t_mma_v(st.O, 0, v0, pb[c]);
-      v6t_read_v<VOFF, 1, 0>(v0, vb);
-      wait_k4<4>(v1);
-      v6t_mma_v(st.O, 4, v1, pb[c]);
-      v6t_read_v<VOFF, 1, 4>(v1, vb);
+      VL::template read<VOFF, 1, 0>(v0, va);
+      VL::template wait<VL::NF>(v1);
+      VL::mma(st.O, 4, v1, pb[c]);
+      VL::template read<VOFF, 1, 4>(v1, va);
     } else {
-      wait_k4<4>(v0);
-      v6t_mma_v(st.O, 0, v0, pb[c]);
-      wait_k4<0>(v1);
-      v6t_mma_v(st.O, 4, v1, pb[c]);
+      VL::template wait<0>(v1);
+      VL::mma(st.O, 4, v1, pb[c]);
     }
   }
 }
@@ -801,17 +835,9 @@ __device__ __forceinline__ void attn_half_block(V6State& st, const bf16x8 (&qf)[
   v6_read_k<KOFF, 0>(k0, ka);
   v6_read_k<KOFF, 1>(k1, ka);
   wait_k4<4>(k0);
-#pragma unroll
-  for (int dc = 0; dc < 4; ++dc) {
-    S[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v6_as_bf8(k0[dc]), qf[0][dc], S[0][0], 0, 0, 0);
-    S[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v6_as_bf8(k0[dc]), qf[1][dc], S[0][1], 0, 0, 0);
-  }
+  v6_mma_k(S, 0, k0, qf);
   wait_k4<0>(k1);
-#pragma unroll
-  for (int dc = 0; dc < 4; ++dc) {
-    S[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v6_as_bf8(k1[dc]), qf[0][dc], S[1][0], 0, 0, 0);
-    S[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v6_as_bf8(k1[dc]), qf[1][dc], S[1][1], 0, 0, 0);
-  }
+  v6_mma_k(S, 1, k1, qf);
   u32x2 v0[8], v1[8];
   v6_read_v<VOFF, 0, 0>(v0, va);
   v6_read_v<VOFF, 0, 4>(v1, va);
@@ -857,13 +883,7 @@ __device__ __forceinline__ void attn_half_block(V6State& st, const bf16x8 (&qf)[
       pb[qt][j] = f2bf(__builtin_amdgcn_exp2f(S[0][qt][j]));
       pb[qt][4 + j] = f2bf(__builtin_amdgcn_exp2f(S[1][qt][j]));
     }
-  {
-    bf16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (bf16)1.0f;
-    st.L[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[0], st.L[0], 0, 0, 0);
-    st.L[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[1], st.L[1], 0, 0, 0);
-  }
+  v6_rowsum(st, pb);
   wait_v<8>(v0);
   v6_mma_v(st.O, 0, v0, pb);
   wait_v<0>(v1);
@@ -872,6 +892,136 @@ __device__ __forceinline__ void attn_half_block(V6State& st, const bf16x8 (&qf)[
 
 namespace {
 
+// ---- pieces every flash body below is built from
+// a 3-D grid (query blocks, heads, segments) flattened, remapped over the XCDs and decoded again
+struct AttnTile {
+  int qb, h, seg;
+};
+__device__ __forceinline__ AttnTile attn_tile(int flat, int nqb, int nheads) {
+  return {flat % nqb, (flat / nqb) % nheads, flat / (nqb * nheads)};
+}
+__device__ __forceinline__ AttnTile attn_grid_tile() {
+  const int nx = gridDim.x, ny = gridDim.y;
+  return attn_tile(xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z), nx, ny);
+}
+
+// a segment (or a block list) without keys: zeros, as SDPA (nothing to add when accumulating)
+template <int QBW>
+__device__ __forceinline__ void attn_zero_rows(const AttnArgs& a, int qb, int h, int q_row0, int q_len) {
+  if (a.accumulate) return;
+  for (int i = threadIdx.x; i < QBW * (D / 8); i += QBW * 2) {  // QBW * 2 threads: a wave per 32 query rows
+    const int qi = qb * QBW + i / (D / 8);
+    if (qi < q_len) {
+      const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
+      *(u32x4*)(a.o + (long)orow * a.os + h * D + (i % (D / 8)) * 8) = (u32x4){0u, 0u, 0u, 0u};
+    }
+  }
+}
+
+// Q as the B operand: query tile qt, d chunk dc: Q[query][dc*32 + 8g .. +7], prescaled by c; this wave's 32 queries
+// from q0 of the segment, rows clamped to the segment
+__device__ __forceinline__ void attn_load_q(bf16x8 (&qf)[2][4], const bf16* q, long qs, float c, int q_row0, int q_len,
+                                            int q0, int h, int g, int r16) {
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const int qc = min(q0 + qt * 16 + r16, q_len - 1);
+    const bf16* qp = q + (long)(q_row0 + qc) * qs + h * D + 8 * g;
+#pragma unroll
+    for (int dc = 0; dc < 4; ++dc) {
+      qf[qt][dc] = *(const bf16x8*)(qp + 32 * dc);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qf[qt][dc][j] = f2bf(bf2f(qf[qt][dc][j]) * c);
+    }
+  }
+}
+
+// per-lane LDS read bases of the K fragments (K tile of stage 0, key tile 0; the rest are +immediate)
+__device__ __forceinline__ void attn_k_bases(uint32_t (&ka)[4], uint32_t lds_k, int g, int r16) {
+#pragma unroll
+  for (int dc = 0; dc < 4; ++dc) ka[dc] = lds_k + r16 * 256 + (((dc * 4 + g) ^ r16) << 4);
+}
+
+// the output address of this lane's 16 bytes of d tiles (0, 1) of one row: lane rows g and g^1 (lanes l, l^16) hold
+// adjacent 4-column groups of one query row, and attn_pair16 below pairs d tiles (dt, dt+1) at + dt * 16 elements
+__device__ __forceinline__ bf16* attn_o_ptr(bf16* o, long row, long os, int h, int g) {
+  return o + row * os + h * D + 4 * (g & ~1) + 16 * (g & 1);
+}
+// one permlane16 swap per dword, so each lane stores 16 contiguous bytes (T21)
+__device__ __forceinline__ u32x4 attn_pair16(bf16x4 pa, bf16x4 pb) {
+  const u32x2 ga = __builtin_bit_cast(u32x2, pa), gb = __builtin_bit_cast(u32x2, pb);
+  const auto rx = __builtin_amdgcn_permlane16_swap(ga[0], gb[0], false, false);
+  const auto ry = __builtin_amdgcn_permlane16_swap(ga[1], gb[1], false, false);
+  return (u32x4){rx[0], ry[0], rx[1], ry[1]};
+}
+
+// the self-attention output of this wave's 32 queries from q0 of the segment: bf16(O / l), added to the bf16 output
+// when accumulating (bf16 + bf16 as the reference's sum of attention outputs, 1B:602)
+__device__ __forceinline__ void attn_store_o(const V6State& st, const AttnArgs& a, int q_row0, int q_len, int q0, int h,
+                                             int g, int r16) {
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    const float inv = 1.0f / st.L[qt][0];
+    const int qi = q0 + qt * 16 + r16;
+    const int qrow = q_row0 + min(qi, q_len - 1);
+    bf16* op = attn_o_ptr(a.o, a.orows ? a.orows[qrow] : qrow, a.os, h, g);
+#pragma unroll
+    for (int dt = 0; dt < 8; dt += 2) {
+      const f32x4& A = st.O[dt][qt];
+      const f32x4& B = st.O[dt + 1][qt];
+      const bf16x4 pa = {f2bf(A[0] * inv), f2bf(A[1] * inv), f2bf(A[2] * inv), f2bf(A[3] * inv)};
+      const bf16x4 pb = {f2bf(B[0] * inv), f2bf(B[1] * inv), f2bf(B[2] * inv), f2bf(B[3] * inv)};
+      u32x4 out = attn_pair16(pa, pb);
+      bf16* p = op + dt * 16;
+      if (a.accumulate) {
+        const bf16x8 ov = *(const bf16x8*)p;
+        bf16x8 nv = __builtin_bit_cast(bf16x8, out);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) nv[j] = f2bf(bf2f(ov[j]) + bf2f(nv[j]));
+        out = __builtin_bit_cast(u32x4, nv);
+      }
+      if (qi < q_len) *(u32x4*)p = out;
+    }
+  }
+}
+
+// the 2-stage ring over n >= 1 blocks: block i runs from stage i & 1 while block i + 1's DMA lands in the other (one
+// block of lead, vmcnt(0) + __syncthreads() per block), the loop unrolled by two so the stage is a compile-time
+// offset.  stage(kb, buf) issues block kb's DMA; block(buf, first, kb) runs it (buf, first: integral constants).
+// LIST: block i is list[i] (a scalar table load), else i itself -- a plain counter.  Over a list, kc is the block being
+// run, kn the one staged behind it, and the entry after that is read (clamped to the list) before the barrier that
+// precedes its staging.  PRIO: the upper four of eight waves raise their priority (waves w and w+4 share a SIMD)
+template <bool LIST, bool PRIO, class Stage, class Block>
+__device__ __forceinline__ void attn_ring2(int n, [[maybe_unused]] const int* list, Stage stage, Block block) {
+  using B0 = std::integral_constant<int, 0>;
+  using B1 = std::integral_constant<int, 1>;
+  auto at = [&](int i) {
+    if constexpr (LIST) return sload(list + min(i, n - 1));
+    else return i;
+  };
+  [[maybe_unused]] int kn = at(1);
+  auto step = [&](int i, auto buf) {  // block i from stage buf, block i + 1 staged behind it
+    const int kc = LIST ? kn : i;
+    kn = at(i + 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (i + 1 < n) stage(kn, 1 - buf());
+    block(buf, std::false_type{}, kc);
+  };
+  const int k0 = at(0);
+  stage(k0, 0);
+  if (PRIO && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (1 < n) stage(kn, 1);
+  block(B0{}, std::true_type{}, k0);
+  for (int i = 1; i < n; i += 2) {
+    step(i, B1{});
+    if (i + 1 >= n) break;
+    step(i + 1, B0{});
+  }
+}
+
+// The self-attention body over a V layout (VRows, VTrans).
 // NW = 8: 256 query rows per workgroup, waves w and w+4 share a SIMD (one workgroup per CU); NW = 4: 128
 // query rows, one wave per SIMD, two workgroups per CU -- the same per-SIMD pairing at half the work
 // granularity, for launches whose 256-row workgroup count leaves the last round over the CUs mostly empty
@@ -881,12 +1031,13 @@ namespace {
 // two halves
 // SPARSE: the block loop runs the query block's list (AttnSparseArgs) instead of 0 .. nkb - 1; an empty list is a
 // segment with no keys
-template <int NW, bool SPLIT = false, bool SPARSE = false>
-__device__ __forceinline__ void attn_fwd_v6_body(const std::conditional_t<SPARSE, AttnSparseArgs, AttnArgs>& a) {
+template <class VL, int NW, bool SPLIT = false, bool SPARSE = false>
+__device__ __forceinline__ void attn_fwd_body(const std::conditional_t<SPARSE, AttnSparseArgs, AttnArgs>& a) {
   static_assert(!SPARSE || (NW == 8 && !SPLIT), "the block list serves the 8-wave whole-tile launches");
   constexpr int QBW = NW * 32, PPW = 16 / NW;  // query rows per workgroup, K (and V) 1-KB pieces per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int qb, h, seg, half = -1, stile = 0;
+  AttnTile t;
+  int half = -1, stile = 0;
   if constexpr (SPLIT) {
     int tile;
     if ((int)blockIdx.x < a.split_full) {
@@ -897,17 +1048,12 @@ __device__ __forceinline__ void attn_fwd_v6_body(const std::conditional_t<SPARSE
       half = idx & 1;
       tile = a.split_full + stile;
     }
-    qb = tile % a.nqb;
-    h = (tile / a.nqb) % a.nheads;
-    seg = tile / (a.nqb * a.nheads);
+    t = attn_tile(tile, a.nqb, a.nheads);
   } else {
-    const int nx = gridDim.x, ny = gridDim.y;
-    const int flat = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z);
-    qb = flat % nx;
-    h = (flat / nx) % ny;
-    seg = flat / (nx * ny);
+    t = attn_grid_tile();
   }
-  const int* sg = a.segs + seg * 4;
+  const int qb = t.qb, h = t.h;
+  const int* sg = a.segs + t.seg * 4;
   const int q_row0 = sg[0], q_len = sg[1];
   int kv_row0 = sg[2], kv_len = sg[3];
   if (SPLIT && half >= 0) {  // this half's keys: whole 64-key blocks in the first half
@@ -937,146 +1083,45 @@ __device__ __forceinline__ void attn_fwd_v6_body(const std::conditional_t<SPARSE
     nbl = sload(a.blk_ptr + qb + 1) - p0;
     bl = a.blk_idx + p0;
   }
-  // a segment with no keys: zeros, as SDPA (nothing to add when accumulating)
-  if (kv_len <= 0 || (SPARSE && nbl <= 0)) {
-    if (!a.accumulate)
-      for (int i = tid; i < QBW * (D / 8); i += NW * 64) {
-        const int qi = qb * QBW + i / (D / 8);
-        if (qi < q_len) {
-          const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
-          *(u32x4*)(a.o + (long)orow * a.os + h * D + (i % (D / 8)) * 8) = (u32x4){0u, 0u, 0u, 0u};
-        }
-      }
-    return;
-  }
+  if (kv_len <= 0 || (SPARSE && nbl <= 0)) return attn_zero_rows<QBW>(a, qb, h, q_row0, q_len);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r16 = lane & 15;
-
-  // Q as the B operand: query tile qt, d chunk dc: Q[query][dc*32 + 8g .. +7], prescaled by c
+  const int q0 = qb * QBW + wave * 32;  // this wave's first query
   bf16x8 qf[2][4];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int qc = min(qb * QBW + wave * 32 + qt * 16 + r16, q_len - 1);
-    const bf16* qp = a.q + (long)(q_row0 + qc) * a.qs + h * D + 8 * g;
-#pragma unroll
-    for (int dc = 0; dc < 4; ++dc) {
-      qf[qt][dc] = *(const bf16x8*)(qp + 32 * dc);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qf[qt][dc][j] = f2bf(bf2f(qf[qt][dc][j]) * a.c);
-    }
-  }
+  attn_load_q(qf, a.q, a.qs, a.c, q_row0, q_len, q0, h, g, r16);
 
-  // K/V pieces: each wave moves 2 x 1-KB pieces (4 rows each) of K and of V per block; lane -> row
-  // (lane / 16), stored position lane % 16 holding source chunk (lane % 16) ^ swizzle(row).  By
-  // buffer_load...lds from SGPR descriptors, per-lane 32-bit offsets and the block in soffset: no 64-bit
-  // address VALU.  The range check takes voffset + soffset + the instruction offset against the records (a V^T
-  // form reading per-source chunks, measured and removed in round 6, read zeros past a records value that left
-  // soffset out); a partial last block is staged from a descriptor of its own (base = its first row, soffset 0)
-  // whose range ends at the segment's last row, so its rows past kv_len read as zeros (masked in S, and 0 x 0 in
-  // PV) instead of whatever follows
+  // K/V pieces: each wave moves PPW x 1-KB pieces of K and of V per block; K lane -> row (lane / 16), stored position
+  // lane % 16 holding source chunk (lane % 16) ^ (row & 15) (conflict-free 16-row b128 reads); V as its layout says
   const int nkb = (kv_len + KVB - 1) / KVB;
-  const long tail0 = (long)(nkb - 1) * KVB;  // first row of the last block
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.k + (long)kv_row0 * a.ks + h * D), (short)0, (int)(((long)kv_len - 1) * a.ks * 2 + 256), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.v + (long)kv_row0 * a.vs + h * D), (short)0, (int)(((long)kv_len - 1) * a.vs * 2 + 256), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rkt = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.k + (kv_row0 + tail0) * a.ks + h * D), (short)0, (int)((kv_len - tail0 - 1) * a.ks * 2 + 256),
-      0x00020000);
-  const __amdgpu_buffer_rsrc_t rvt = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.v + (kv_row0 + tail0) * a.vs + h * D), (short)0, (int)((kv_len - tail0 - 1) * a.vs * 2 + 256),
-      0x00020000);
   const bool ragged = kv_len % KVB != 0;
+  const RowRsrc rk = attn_row_rsrc(a.k, a.ks, kv_row0, kv_len, h);
+  const typename VL::Src rv = VL::src(a.v, a.vs, kv_row0, kv_len, h);
   int koff[PPW], voff[PPW];
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
-    const int srow = (wave * PPW + i) * 4 + (lane >> 4);
+    const int srow = (wave * PPW + i) * 4 + g;
     koff[i] = srow * (int)a.ks * 2 + ((r16 ^ (srow & 15)) << 4);
-    voff[i] = srow * (int)a.vs * 2 + ((r16 ^ ((srow & 7) << 1)) << 4);
+    voff[i] = VL::off(wave * PPW + i, lane, (int)a.vs);
   }
-  const uint32_t lds_dma = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)LDS_PTR(smem) + wave * PPW * 1024);
-  auto stage = [&](int kb, int buf) {
+  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
+  const uint32_t lds_dma = __builtin_amdgcn_readfirstlane(lds0 + wave * PPW * 1024);
+  auto stage = [&](int kb, int buf) {  // LDS: 2 stages as K | V pairs
     const bool tail = ragged && kb == nkb - 1;  // wave-uniform
-    const int ks_off = tail ? 0 : kb * KVB * (int)a.ks * 2, vs_off = tail ? 0 : kb * KVB * (int)a.vs * 2;
-    const __amdgpu_buffer_rsrc_t bk = tail ? rkt : rk, bv = tail ? rvt : rv;
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(bk, LDS_PTR((uintptr_t)(lds_dma + buf * STAGE_BYTES + i * 1024)), 16,
-                                               koff[i], ks_off, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          bv, LDS_PTR((uintptr_t)(lds_dma + buf * STAGE_BYTES + TILE_BYTES + i * 1024)), 16, voff[i], vs_off, 0, 0);
+      attn_row_load(rk, tail, kb, (int)a.ks, lds_dma + buf * STAGE_BYTES + i * 1024, koff[i]);
+      VL::load(rv, tail, kb, (int)a.vs, lds_dma + buf * STAGE_BYTES + TILE_BYTES + i * 1024, voff[i]);
     }
   };
-
-  // per-lane LDS read bases (stage 0, key tile / chunk 0); the rest are +immediate
-  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-  uint32_t ka[4], va[8];
-#pragma unroll
-  for (int dc = 0; dc < 4; ++dc) ka[dc] = lds0 + r16 * 256 + (((dc * 4 + g) ^ r16) << 4);
-  {
-    const int q = r16 >> 2, p = r16 & 3;
-    const int row = 4 * g + q;  // + 32 c (+16): same swizzle
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      const int ch = 2 * dt + (p >> 1);
-      va[dt] = lds0 + row * 256 + ((ch ^ ((row & 7) << 1)) << 4) + 8 * (p & 1);
-    }
-  }
+  uint32_t ka[4], va[VL::NBASE];
+  attn_k_bases(ka, lds0, g, r16);
+  VL::bases(va, lds0, g, r16);  // stage 0's V tile is TILE_BYTES on: in the blocks' VOFF
 
   V6State st;
-#pragma unroll
-  for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) st.O[dt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  st.L[0] = st.L[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  st.negm[0] = st.negm[1] = 0.f;
-  st.negm4[0] = st.negm4[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if constexpr (SPARSE) {
-    // the dense loop below over list positions: kc is the block being run, kn the one staged behind it, and the entry
-    // after that is read (clamped to the list) before the barrier that precedes its staging
-    auto at = [&](int i) { return sload(bl + min(i, nbl - 1)); };
-    int kc = at(0), kn = at(1);
-    stage(kc, 0);
-    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (1 < nbl) stage(kn, 1);
-    attn_v6_block<0, TILE_BYTES, true>(st, qf, ka, va, kc, kv_len, g);
-    for (int i = 1; i < nbl; i += 2) {
-      kc = kn;
-      kn = at(i + 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (i + 1 < nbl) stage(kn, 0);
-      attn_v6_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, va, kc, kv_len, g);
-      if (i + 1 >= nbl) break;
-      kc = kn;
-      kn = at(i + 2);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (i + 2 < nbl) stage(kn, 1);
-      attn_v6_block<0, TILE_BYTES, false>(st, qf, ka, va, kc, kv_len, g);
-    }
-  } else {
-    stage(0, 0);
-    if (NW == 8 && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (1 < nkb) stage(1, 1);
-    attn_v6_block<0, TILE_BYTES, true>(st, qf, ka, va, 0, kv_len, g);
-    for (int kb = 1; kb < nkb; kb += 2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (kb + 1 < nkb) stage(kb + 1, 0);
-      attn_v6_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, va, kb, kv_len, g);
-      if (kb + 1 >= nkb) break;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (kb + 2 < nkb) stage(kb + 2, 1);
-      attn_v6_block<0, TILE_BYTES, false>(st, qf, ka, va, kb + 1, kv_len, g);
-    }
-  }
+  st.reset();
+  attn_ring2<SPARSE, NW == 8>(SPARSE ? nbl : nkb, bl, stage, [&](auto buf, auto first, int kb) {
+    attn_v6_block<VL, buf() * STAGE_BYTES, buf() * STAGE_BYTES + TILE_BYTES, first()>(st, qf, ka, va, kb, kv_len, g);
+  });
 
   if (SPLIT && half >= 0) {  // partials: O^T[d][query] of this lane's d = 16 dt + 4 g + i, the query's max and sum
 #pragma unroll
@@ -1091,208 +1136,7 @@ __device__ __forceinline__ void attn_fwd_v6_body(const std::conditional_t<SPARSE
     }
     return;
   }
-  // lane rows g and g^1 (lanes l, l^16) hold adjacent 4-column groups of one query row: one
-  // permlane16 swap per dword pairs d tiles (dt, dt+1) so each lane stores 16 contiguous bytes (T21)
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const float inv = 1.0f / st.L[qt][0];
-    const int qi = qb * QBW + wave * 32 + qt * 16 + r16;
-    const int qrow = q_row0 + min(qi, q_len - 1);
-    const int orow = a.orows ? a.orows[qrow] : qrow;
-    bf16* op = a.o + (long)orow * a.os + h * D + 4 * (g & ~1) + 16 * (g & 1);
-#pragma unroll
-    for (int dt = 0; dt < 8; dt += 2) {
-      const f32x4& A = st.O[dt][qt];
-      const f32x4& B = st.O[dt + 1][qt];
-      const bf16x4 pa = {f2bf(A[0] * inv), f2bf(A[1] * inv), f2bf(A[2] * inv), f2bf(A[3] * inv)};
-      const bf16x4 pb = {f2bf(B[0] * inv), f2bf(B[1] * inv), f2bf(B[2] * inv), f2bf(B[3] * inv)};
-      const u32x2 ga = __builtin_bit_cast(u32x2, pa), gb = __builtin_bit_cast(u32x2, pb);
-      const auto rx = __builtin_amdgcn_permlane16_swap(ga[0], gb[0], false, false);
-      const auto ry = __builtin_amdgcn_permlane16_swap(ga[1], gb[1], false, false);
-      u32x4 out = {rx[0], ry[0], rx[1], ry[1]};
-      bf16* p = op + dt * 16;
-      if (a.accumulate) {  // bf16 + bf16 as the reference's sum of attention outputs (1B:602)
-        const bf16x8 ov = *(const bf16x8*)p;
-        bf16x8 nv = __builtin_bit_cast(bf16x8, out);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) nv[j] = f2bf(bf2f(ov[j]) + bf2f(nv[j]));
-        out = __builtin_bit_cast(u32x4, nv);
-      }
-      if (qi < q_len) *(u32x4*)p = out;
-    }
-  }
-}
-
-// self-attention reading V as V^T (attn_v6t_block above): 8 waves x 32 queries, the v6 ring and K staging.
-// a.v = V^T [heads * 128][Rv] bf16 (row h*128 + d, keys permuted per 32 as P; a.vs = Rv >= the columns any
-// segment's last 64-key block reaches, i.e. kv_row0 + ceil64(kv_len); segments start on 32-key boundaries; every
-// element of a row readable and finite through that block: the partial last block reads the keys past kv_len,
-// masked to P = 0).  2-stage K/V ring: block kb+1's DMA issued at block kb (one block of lead, vmcnt(0) +
-// __syncthreads() per block).
-// SPARSE: as attn_fwd_v6_body's
-template <bool SPARSE = false>
-__device__ __forceinline__ void attn_fwd_vt_body(const std::conditional_t<SPARSE, AttnSparseArgs, AttnArgs>& a) {
-  constexpr int NW = 8, QBW = NW * 32, PPW = 16 / NW;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nx = gridDim.x, ny = gridDim.y;
-  const int flat = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z);
-  const int qb = flat % nx, h = (flat / nx) % ny, seg = flat / (nx * ny);
-  const int* sg = a.segs + seg * 4;
-  const int q_row0 = sg[0], q_len = sg[1], kv_row0 = sg[2], kv_len = sg[3];
-  if (qb * QBW >= q_len) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  [[maybe_unused]] const int* bl = nullptr;
-  [[maybe_unused]] int nbl = 0;
-  if constexpr (SPARSE) {
-    const int p0 = sload(a.blk_ptr + qb);
-    nbl = sload(a.blk_ptr + qb + 1) - p0;
-    bl = a.blk_idx + p0;
-  }
-  if (kv_len <= 0 || (SPARSE && nbl <= 0)) {
-    if (!a.accumulate)
-      for (int i = tid; i < QBW * (D / 8); i += NW * 64) {
-        const int qi = qb * QBW + i / (D / 8);
-        if (qi < q_len) {
-          const int orow = a.orows ? a.orows[q_row0 + qi] : q_row0 + qi;
-          *(u32x4*)(a.o + (long)orow * a.os + h * D + (i % (D / 8)) * 8) = (u32x4){0u, 0u, 0u, 0u};
-        }
-      }
-    return;
-  }
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, r16 = lane & 15;
-  bf16x8 qf[2][4];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int qc = min(qb * QBW + wave * 32 + qt * 16 + r16, q_len - 1);
-    const bf16* qp = a.q + (long)(q_row0 + qc) * a.qs + h * D + 8 * g;
-#pragma unroll
-    for (int dc = 0; dc < 4; ++dc) {
-      qf[qt][dc] = *(const bf16x8*)(qp + 32 * dc);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qf[qt][dc][j] = f2bf(bf2f(qf[qt][dc][j]) * a.c);
-    }
-  }
-  const int nkb = (kv_len + KVB - 1) / KVB;
-  const long tail0 = (long)(nkb - 1) * KVB;
-  const bool ragged = kv_len % KVB != 0;
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.k + (long)kv_row0 * a.ks + h * D), (short)0, (int)(((long)kv_len - 1) * a.ks * 2 + 256), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rkt = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.k + (kv_row0 + tail0) * a.ks + h * D), (short)0, (int)((kv_len - tail0 - 1) * a.ks * 2 + 256),
-      0x00020000);
-  // V^T: the head's 128 d-rows from key kv_row0, each through the segment's last block
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.v + (long)h * D * a.vs + kv_row0), (short)0, (int)(((long)(D - 1) * a.vs + (long)nkb * KVB) * 2),
-      0x00020000);
-  const int dw = wave;  // this wave's share of the K / V pieces
-  int koff[PPW], voff[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int srow = (dw * PPW + i) * 4 + (lane >> 4);
-    koff[i] = srow * (int)a.ks * 2 + ((r16 ^ (srow & 15)) << 4);
-    const int d = (dw * PPW + i) * 8 + (lane >> 3);  // a 1-KB piece = 8 d-rows x 128 B
-    voff[i] = d * (int)a.vs * 2 + (((lane & 7) ^ (d & 7)) << 4);
-  }
-  const uint32_t lds_dma = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)LDS_PTR(smem) + dw * PPW * 1024);
-  auto stage = [&](int kb, int buf) {  // LDS: 2 stages as K | V pairs
-    const bool tail = ragged && kb == nkb - 1;
-    const int ks_off = tail ? 0 : kb * KVB * (int)a.ks * 2, vs_off = kb * KVB * 2;
-    const __amdgpu_buffer_rsrc_t bk = tail ? rkt : rk;
-    const int kdst = buf * STAGE_BYTES, vdst = buf * STAGE_BYTES + TILE_BYTES;
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(bk, LDS_PTR((uintptr_t)(lds_dma + kdst + i * 1024)), 16, koff[i],
-                                               ks_off, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, LDS_PTR((uintptr_t)(lds_dma + vdst + i * 1024)), 16, voff[i],
-                                               vs_off, 0, 0);
-    }
-  };
-  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-  uint32_t ka[4], vb[2];
-#pragma unroll
-  for (int dc = 0; dc < 4; ++dc) ka[dc] = lds0 + r16 * 256 + (((dc * 4 + g) ^ r16) << 4);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) vb[c] = lds0 + r16 * 128 + (((4 * c + g) ^ (r16 & 7)) << 4);
-
-  V6State st;
-#pragma unroll
-  for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) st.O[dt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  st.L[0] = st.L[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  st.negm[0] = st.negm[1] = 0.f;
-  st.negm4[0] = st.negm4[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto sync = [] {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  if constexpr (SPARSE) {  // the dense loop below over list positions (kc, kn, at: as in attn_fwd_v6_body)
-    auto at = [&](int i) { return sload(bl + min(i, nbl - 1)); };
-    int kc = at(0), kn = at(1);
-    stage(kc, 0);
-    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-    sync();
-    if (1 < nbl) stage(kn, 1);
-    attn_v6t_block<0, TILE_BYTES, true>(st, qf, ka, vb, kc, kv_len, g);
-    for (int i = 1; i < nbl; i += 2) {
-      kc = kn;
-      kn = at(i + 1);
-      sync();
-      if (i + 1 < nbl) stage(kn, 0);
-      attn_v6t_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, vb, kc, kv_len, g);
-      if (i + 1 >= nbl) break;
-      kc = kn;
-      kn = at(i + 2);
-      sync();
-      if (i + 2 < nbl) stage(kn, 1);
-      attn_v6t_block<0, TILE_BYTES, false>(st, qf, ka, vb, kc, kv_len, g);
-    }
-  } else {
-    stage(0, 0);
-    if (__builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
-    sync();
-    if (1 < nkb) stage(1, 1);
-    attn_v6t_block<0, TILE_BYTES, true>(st, qf, ka, vb, 0, kv_len, g);
-    for (int kb = 1; kb < nkb; kb += 2) {
-      sync();
-      if (kb + 1 < nkb) stage(kb + 1, 0);
-      attn_v6t_block<STAGE_BYTES, STAGE_BYTES + TILE_BYTES, false>(st, qf, ka, vb, kb, kv_len, g);
-      if (kb + 1 >= nkb) break;
-      sync();
-      if (kb + 2 < nkb) stage(kb + 2, 1);
-      attn_v6t_block<0, TILE_BYTES, false>(st, qf, ka, vb, kb + 1, kv_len, g);
-    }
-  }
-
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const float inv = 1.0f / st.L[qt][0];
-    const int qi = qb * QBW + wave * 32 + qt * 16 + r16;
-    const int qrow = q_row0 + min(qi, q_len - 1);
-    const int orow = a.orows ? a.orows[qrow] : qrow;
-    bf16* op = a.o + (long)orow * a.os + h * D + 4 * (g & ~1) + 16 * (g & 1);
-#pragma unroll
-    for (int dt = 0; dt < 8; dt += 2) {
-      const f32x4& A = st.O[dt][qt];
-      const f32x4& B = st.O[dt + 1][qt];
-      const bf16x4 pa = {f2bf(A[0] * inv), f2bf(A[1] * inv), f2bf(A[2] * inv), f2bf(A[3] * inv)};
-      const bf16x4 pb = {f2bf(B[0] * inv), f2bf(B[1] * inv), f2bf(B[2] * inv), f2bf(B[3] * inv)};
-      const u32x2 ga = __builtin_bit_cast(u32x2, pa), gb = __builtin_bit_cast(u32x2, pb);
-      const auto rx = __builtin_amdgcn_permlane16_swap(ga[0], gb[0], false, false);
-      const auto ry = __builtin_amdgcn_permlane16_swap(ga[1], gb[1], false, false);
-      u32x4 out = {rx[0], ry[0], rx[1], ry[1]};
-      bf16* p = op + dt * 16;
-      if (a.accumulate) {
-        const bf16x8 ov = *(const bf16x8*)p;
-        bf16x8 nv = __builtin_bit_cast(bf16x8, out);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) nv[j] = f2bf(bf2f(ov[j]) + bf2f(nv[j]));
-        out = __builtin_bit_cast(u32x4, nv);
-      }
-      if (qi < q_len) *(u32x4*)p = out;
-    }
-  }
+  attn_store_o(st, a, q_row0, q_len, q0, h, g, r16);
 }
 
 // the fused cross-attention on the self-attention block body: 8 waves x 32 queries of one query block,
@@ -1305,29 +1149,16 @@ __device__ __forceinline__ void attn_cross3_body(const Cross3Args& a) {
   constexpr int QBW = NW * 32, PPW = 16 / NW;  // queries per workgroup, K (and V) 1-KB pieces per wave per block
   constexpr int VBASE = NST * TILE_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nx = gridDim.x, ny = gridDim.y;
-  const int flat = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nx * ny * gridDim.z);
-  const int qb = flat % nx, h = (flat / nx) % ny, b = flat / (nx * ny);
+  const AttnTile t = attn_grid_tile();
+  const int qb = t.qb, h = t.h, b = t.seg;
   if (qb * QBW >= a.q_len) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r16 = lane & 15;
-  const int q_row0 = b * a.q_len;
+  const int q_row0 = b * a.q_len, q0 = qb * QBW + wave * 32;
   const int frame = (a.tok_offset + qb * QBW) / a.tpf;
-
-  // Q as the B operand (query tile qt, d chunk dc), prescaled by c; rows clamped to the segment
   bf16x8 qf[2][4];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int qc = min(qb * QBW + wave * 32 + qt * 16 + r16, a.q_len - 1);
-    const bf16* qp = a.q + (long)(q_row0 + qc) * a.qs + h * D + 8 * g;
-#pragma unroll
-    for (int dc = 0; dc < 4; ++dc) {
-      qf[qt][dc] = *(const bf16x8*)(qp + 32 * dc);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qf[qt][dc][j] = f2bf(bf2f(qf[qt][dc][j]) * a.c);
-    }
-  }
+  attn_load_q(qf, a.q, a.qs, a.c, q_row0, a.q_len, q0, h, g, r16);
 
   // block stream: text blocks, image blocks, vocal block(s); LDS images as the self-attention kernel's
   // (K rows chunk ^ (row & 15), V rows chunk ^ 2 (row & 7)); each wave moves 2 x 1-KB pieces of K and V
@@ -1377,28 +1208,13 @@ __device__ __forceinline__ void attn_cross3_body(const Cross3Args& a) {
 
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
   uint32_t ka[4], va[8];
-#pragma unroll
-  for (int dc = 0; dc < 4; ++dc) ka[dc] = lds0 + r16 * 256 + (((dc * 4 + g) ^ r16) << 4);
-  {
-    const int q4 = r16 >> 2, p4 = r16 & 3;
-    const int row = 4 * g + q4;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      const int ch = 2 * dt + (p4 >> 1);
-      va[dt] = lds0 + VBASE + row * 256 + ((ch ^ ((row & 7) << 1)) << 4) + 8 * (p4 & 1);
-    }
-  }
+  attn_k_bases(ka, lds0, g, r16);
+  VRows::bases(va, lds0 + VBASE, g, r16);
 
   V6State st;
-  auto reset = [&]() {
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) st.O[dt][qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    st.L[0] = st.L[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    st.negm[0] = st.negm[1] = 0.f;
-    st.negm4[0] = st.negm4[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  };
+  // through a lambda of this body: with finish() below calling st.reset() itself, hipcc schedules the block loop
+  // differently (the same instructions, 6 / 3 more s_nop cycles per block, 0.7 % / 0.3 % per launch at config 2)
+  auto reset = [&]() { st.reset(); };
   reset();
   bf16x4 acc[8][2];  // running (text + img) + vocal, bf16 as in the reference
   // finish source `src` (0 text, 1 image, 2 vocal): bf16(O / l) folded into acc
@@ -1446,7 +1262,7 @@ __device__ __forceinline__ void attn_cross3_body(const Cross3Args& a) {
     const int kb = src == 0 ? jj : (src == 1 ? jj - nT : jj - nT - nI);
     const int len = src == 0 ? a.t_len : (src == 1 ? a.i_len : a.nper);
     at_slot(jj % NST);
-    attn_v6_block<0, 0, false, false>(st, qf, kas, vas, kb, len, g, kb == 0);
+    attn_v6_block<VRows, 0, 0, false, false>(st, qf, kas, vas, kb, len, g, kb == 0);
     if (jj == nT - 1 || jj == nT + nI - 1 || jj == ntot - 1) finish(src);
   };
   // the vocal stream's single block when a frame has at most 32 audio tokens (StableAvatar: 32), and the image
@@ -1476,14 +1292,12 @@ __device__ __forceinline__ void attn_cross3_body(const Cross3Args& a) {
   // 16-byte stores from permlane16-swapped column-group pairs, as the self-attention epilogue (T21)
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    const int qi = qb * QBW + wave * 32 + qt * 16 + r16;
-    bf16* op = a.o + (long)(q_row0 + min(qi, a.q_len - 1)) * a.os + h * D + 4 * (g & ~1) + 16 * (g & 1);
+    const int qi = q0 + qt * 16 + r16;
+    bf16* op = attn_o_ptr(a.o, q_row0 + min(qi, a.q_len - 1), a.os, h, g);
 #pragma unroll
     for (int dt = 0; dt < 8; dt += 2) {
-      const u32x2 ga = __builtin_bit_cast(u32x2, acc[dt][qt]), gb = __builtin_bit_cast(u32x2, acc[dt + 1][qt]);
-      const auto rx = __builtin_amdgcn_permlane16_swap(ga[0], gb[0], false, false);
-      const auto ry = __builtin_amdgcn_permlane16_swap(ga[1], gb[1], false, false);
-      if (qi < a.q_len) *(u32x4*)(op + dt * 16) = (u32x4){rx[0], ry[0], rx[1], ry[1]};
+      const u32x4 out = attn_pair16(acc[dt][qt], acc[dt + 1][qt]);
+      if (qi < a.q_len) *(u32x4*)(op + dt * 16) = out;
     }
   }
 }
@@ -1493,14 +1307,15 @@ __global__ __launch_bounds__(512) void attn_cross3_kernel(Cross3Args a) { attn_c
 // stores run beside the other's blocks
 __global__ __launch_bounds__(256, 2) void attn_cross3_w4_kernel(Cross3Args a) { attn_cross3_body<4, 2>(a); }
 
-__global__ __launch_bounds__(512) void attn_fwd_v6_kernel(AttnArgs a) { attn_fwd_v6_body<8>(a); }
-__global__ __launch_bounds__(512) void attn_fwd_v6_split_kernel(AttnArgs a) { attn_fwd_v6_body<8, true>(a); }
+__global__ __launch_bounds__(512) void attn_fwd_v6_kernel(AttnArgs a) { attn_fwd_body<VRows, 8>(a); }
+__global__ __launch_bounds__(512) void attn_fwd_v6_split_kernel(AttnArgs a) { attn_fwd_body<VRows, 8, true>(a); }
 
 // the two key halves of each split tile -> the output: O = (w0 O0 + w1 O1) / (w0 l0 + w1 l1), w = 2^(m - max(m0, m1))
 __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a) {
   const int stile = blockIdx.x, tile = a.split_full + stile;
-  const int qb = tile % a.nqb, h = (tile / a.nqb) % a.nheads, seg = tile / (a.nqb * a.nheads);
-  const int* sg = a.segs + seg * 4;
+  const AttnTile t = attn_tile(tile, a.nqb, a.nheads);
+  const int qb = t.qb, h = t.h;
+  const int* sg = a.segs + t.seg * 4;
   const int q_row0 = sg[0], q_len = sg[1];
   if (qb * QB >= q_len) return;
   const float* w0 = a.work + (long)stile * 2 * QB * (D + 2);
@@ -1528,15 +1343,38 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a) {
     *(bf16x4*)p = o4;
   }
 }
-__global__ __launch_bounds__(256, 2) void attn_fwd_v6_w4_kernel(AttnArgs a) { attn_fwd_v6_body<4>(a); }
-__global__ __launch_bounds__(512) void attn_fwd_v6t_kernel(AttnArgs a) { attn_fwd_vt_body(a); }
-// the block-sparse launches of the two 8-wave bodies (sa_attn_fwd_sparse)
+__global__ __launch_bounds__(256, 2) void attn_fwd_v6_w4_kernel(AttnArgs a) { attn_fwd_body<VRows, 4>(a); }
+__global__ __launch_bounds__(512) void attn_fwd_v6t_kernel(AttnArgs a) { attn_fwd_body<VTrans, 8>(a); }
+// the block-sparse launches of the two 8-wave kernels (sa_attn_fwd_sparse)
 __global__ __launch_bounds__(512) void attn_fwd_v6_sparse_kernel(AttnSparseArgs a) {
-  attn_fwd_v6_body<8, false, true>(a);
+  attn_fwd_body<VRows, 8, false, true>(a);
 }
-__global__ __launch_bounds__(512) void attn_fwd_v6t_sparse_kernel(AttnSparseArgs a) { attn_fwd_vt_body<true>(a); }
+__global__ __launch_bounds__(512) void attn_fwd_v6t_sparse_kernel(AttnSparseArgs a) {
+  attn_fwd_body<VTrans, 8, false, true>(a);
+}
 
 }  // namespace
+
+// what the three self-attention entries check alike; vt: v is V^T (rows of whole 64-key blocks)
+static bool self_attn_args_ok(const void* q, const void* k, const void* v, const void* o, const int32_t* segs, int nseg,
+                              int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
+                              int64_t v_stride, int64_t o_stride, bool vt) {
+  if (!q || !k || !v || !o || !segs || nseg <= 0 || max_q_len <= 0 || heads <= 0 || head_dim != D) return false;
+  if ((q_stride | k_stride | v_stride | o_stride) % 8) return false;
+  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return false;
+  return !(vt && (v_stride % 64 || (((uintptr_t)v) & 127)));
+}
+static AttnArgs make_args(const void* q, const void* k, const void* v, void* o, const int32_t* segs, int64_t q_stride,
+                          int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale, int accumulate,
+                          const int32_t* o_rows) {
+  return AttnArgs{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, segs, q_stride, k_stride, v_stride,
+                  o_stride, scale * 1.4426950408889634f, accumulate, o_rows};
+}
+// the kernels' dynamic LDS above the default limit: the initialiser of a function-local static (one-time, thread-safe)
+static bool allow_lds(std::initializer_list<const void*> kernels, int bytes) {
+  for (const void* f : kernels) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return true;
+}
 
 // kernel: 0 = auto, 1 = attn_fwd_v6_kernel (8 waves x 32 queries, mfma_f32_16x16x32_bf16), 2 = the 4-wave
 // attn_fwd_v6_w4_kernel (two workgroups per CU).  Auto estimates both launches in rounds of one 8-wave
@@ -1550,22 +1388,14 @@ extern "C" int sa_attn_fwd_map(const void* q, const void* k, const void* v, void
                                int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
                                int64_t v_stride, int64_t o_stride, float scale, int accumulate, int kernel,
                                const int32_t* o_rows, void* stream) {
-  if (!q || !k || !v || !o || !segs || nseg <= 0 || max_q_len <= 0 || heads <= 0) return SA_ERR_ARG;
-  if (head_dim != D) return SA_ERR_ARG;
-  if ((q_stride | k_stride | v_stride | o_stride) % 8) return SA_ERR_ARG;
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return SA_ERR_ARG;
   if (kernel < 0 || kernel > 3) return SA_ERR_ARG;
-  if (kernel == 3 && (v_stride % 64 || (((uintptr_t)v) & 127))) return SA_ERR_ARG;  // V^T rows: whole 64-key blocks
-  static const bool attr = [] {  // one-time, thread-safe
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6_w4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6t_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    return true;
-  }();
+  if (!self_attn_args_ok(q, k, v, o, segs, nseg, max_q_len, heads, head_dim, q_stride, k_stride, v_stride, o_stride,
+                         kernel == 3))
+    return SA_ERR_ARG;
+  static const bool attr = allow_lds({(const void*)attn_fwd_v6_kernel, (const void*)attn_fwd_v6_w4_kernel,
+                                      (const void*)attn_fwd_v6t_kernel}, LDS_BYTES);
   (void)attr;
-  AttnArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, segs,
-             q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, accumulate, o_rows};
+  const AttnArgs a = make_args(q, k, v, o, segs, q_stride, k_stride, v_stride, o_stride, scale, accumulate, o_rows);
   if (kernel == 0) {
     static int cus[64] = {0};  // per device, queried once
     int dev = 0, ncu = 256;
@@ -1582,7 +1412,7 @@ extern "C" int sa_attn_fwd_map(const void* q, const void* k, const void* v, void
   if (kernel == 2) {
     dim3 grid((max_q_len + 127) / 128, heads, nseg);
     hipLaunchKernelGGL(attn_fwd_v6_w4_kernel, grid, dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-  } else if (kernel == 3) {  // v = V^T [heads * 128][v_stride] (attn_fwd_vt_body)
+  } else if (kernel == 3) {  // v = V^T [heads * 128][v_stride] (VTrans)
     dim3 grid((max_q_len + QB - 1) / QB, heads, nseg);
     hipLaunchKernelGGL(attn_fwd_v6t_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
   } else {
@@ -1600,25 +1430,17 @@ extern "C" int sa_attn_fwd_sparse(const void* q, const void* k, const void* v, v
                                   int64_t v_stride, int64_t o_stride, float scale, int accumulate, int kernel,
                                   const int32_t* o_rows, const int32_t* blk_ptr, const int32_t* blk_idx, int n_qblocks,
                                   void* stream) {
-  if (!q || !k || !v || !o || !segs || nseg <= 0 || max_q_len <= 0 || heads <= 0) return SA_ERR_ARG;
-  if (head_dim != D) return SA_ERR_ARG;
-  if ((q_stride | k_stride | v_stride | o_stride) % 8) return SA_ERR_ARG;
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return SA_ERR_ARG;
   if (kernel != 0 && kernel != 1 && kernel != 3) return SA_ERR_ARG;
-  if (kernel == 3 && (v_stride % 64 || (((uintptr_t)v) & 127))) return SA_ERR_ARG;  // V^T rows: whole 64-key blocks
+  if (!self_attn_args_ok(q, k, v, o, segs, nseg, max_q_len, heads, head_dim, q_stride, k_stride, v_stride, o_stride,
+                         kernel == 3))
+    return SA_ERR_ARG;
   if (!blk_ptr || !blk_idx || ((((uintptr_t)blk_ptr) | ((uintptr_t)blk_idx)) & 3)) return SA_ERR_ARG;
   if (n_qblocks != (max_q_len + QB - 1) / QB) return SA_ERR_ARG;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6t_sparse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    return true;
-  }();
+  static const bool attr =
+      allow_lds({(const void*)attn_fwd_v6_sparse_kernel, (const void*)attn_fwd_v6t_sparse_kernel}, LDS_BYTES);
   (void)attr;
-  AttnSparseArgs a{{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, segs,
-                    q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, accumulate, o_rows},
-                   blk_ptr, blk_idx};
+  const AttnSparseArgs a{make_args(q, k, v, o, segs, q_stride, k_stride, v_stride, o_stride, scale, accumulate, o_rows),
+                         blk_ptr, blk_idx};
   const dim3 grid(n_qblocks, heads, nseg);
   if (kernel == 3) hipLaunchKernelGGL(attn_fwd_v6t_sparse_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(attn_fwd_v6_sparse_kernel, grid, dim3(512), LDS_BYTES, (hipStream_t)stream, a);
@@ -1630,22 +1452,18 @@ extern "C" int sa_attn_fwd_split(const void* q, const void* k, const void* v, vo
                                  int max_q_len, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
                                  int64_t v_stride, int64_t o_stride, float scale, int accumulate, const int32_t* o_rows,
                                  int split_tiles, void* work, int64_t work_bytes, void* stream) {
-  if (!q || !k || !v || !o || !segs || nseg <= 0 || max_q_len <= 0 || heads <= 0 || head_dim != D) return SA_ERR_ARG;
-  if ((q_stride | k_stride | v_stride | o_stride) % 8) return SA_ERR_ARG;
-  if ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o)) & 15) return SA_ERR_ARG;
+  if (!self_attn_args_ok(q, k, v, o, segs, nseg, max_q_len, heads, head_dim, q_stride, k_stride, v_stride, o_stride,
+                         false))
+    return SA_ERR_ARG;
   const int nqb = (max_q_len + QB - 1) / QB;
   const long ntiles = (long)nseg * heads * nqb;
   if (split_tiles <= 0 || split_tiles > ntiles) return SA_ERR_ARG;
   if (!work || (((uintptr_t)work) & 15) || work_bytes < (int64_t)split_tiles * 2 * QB * (D + 2) * 4) return SA_ERR_ARG;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_v6_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    return true;
-  }();
+  static const bool attr = allow_lds({(const void*)attn_fwd_v6_split_kernel}, LDS_BYTES);
   (void)attr;
-  AttnArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, segs,
-             q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, accumulate, o_rows,
-             nqb, heads, (int)(ntiles - split_tiles), split_tiles, (float*)work};
+  AttnArgs a = make_args(q, k, v, o, segs, q_stride, k_stride, v_stride, o_stride, scale, accumulate, o_rows);
+  a.nqb = nqb, a.nheads = heads, a.split_full = (int)(ntiles - split_tiles), a.split_n = split_tiles;
+  a.work = (float*)work;
   hipLaunchKernelGGL(attn_fwd_v6_split_kernel, dim3((unsigned)(ntiles + split_tiles)), dim3(512), LDS_BYTES,
                      (hipStream_t)stream, a);
   SA_LAUNCH_CHECK();
@@ -1684,12 +1502,8 @@ extern "C" int sa_attn_cross3(const void* q, int64_t q_stride, const void* kt, c
   if ((((uintptr_t)q) | ((uintptr_t)kt) | ((uintptr_t)vt) | ((uintptr_t)ki) | ((uintptr_t)vi) | ((uintptr_t)kv) |
        ((uintptr_t)vv) | ((uintptr_t)o)) & 15)
     return SA_ERR_ARG;
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)attn_cross3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-    (void)hipFuncSetAttribute((const void*)attn_cross3_w4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * TILE_BYTES);
-    return true;
-  }();
+  static const bool attr = allow_lds({(const void*)attn_cross3_kernel}, X3_LDS) &&
+                           allow_lds({(const void*)attn_cross3_w4_kernel}, 4 * TILE_BYTES);
   (void)attr;
   Cross3Args a{(const bf16*)q, q_stride, (const bf16*)kt, (const bf16*)vt, t_stride, t_len, (const bf16*)ki,
                (const bf16*)vi, i_stride, i_len, (const bf16*)kv, (const bf16*)vv, v_stride, nper,

@@ -89,10 +89,6 @@ struct SplitArgs {
 constexpr int WBLK = QBW * (D + 2);  // floats per (split tile, half)
 
 template <int OFF>
-__device__ __forceinline__ void ds_b128(u32x4& d, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
-}
-template <int OFF>
 __device__ __forceinline__ void ds_u8(uint32_t& d, uint32_t addr) {
   asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
 }
@@ -102,9 +98,6 @@ __device__ __forceinline__ i32x8 join(const u32x4& lo, const u32x4& hi) {
 // c += a (16 rows on the accumulator's 4 g + e axis) x b (16 rows on the lane axis), e4m3, scale byte 0 of sa / sb
 __device__ __forceinline__ f32x4 mma(const i32x8& a, const i32x8& b, const f32x4& c, int sa, int sb) {
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, sa, 0, sb);
-}
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
 }
 
 // the fragments of four 16-row tiles T0 .. T0 + 3 of a staged tile (rows 16 t + r16, 16-byte chunks g and 4 + g) and

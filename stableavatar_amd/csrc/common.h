@@ -40,6 +40,22 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// non-canonicalising f32 max (MFMA outputs are never signalling NaNs): fmaxf makes hipcc insert a
+// v_max_f32 x, x canonicalisation per operand (MI355X_MICROARCH.md, App. B attention pitfalls).  The
+// IEEE-2019 maximum lowers to gfx950's v_maximum3_f32 with no canonicalisation, and, unlike an inline-asm
+// v_max3_f32, needs no conservative s_nop after each link of a dependent chain (hipcc pads every VGPR an
+// asm statement defines before the next VALU reads it: 16+ s_nop per block on the attention rescale test)
+__device__ __forceinline__ float vmax3(float a, float b, float c) {
+  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c);
+}
+// LDS reads issued from inline asm at base+immediate addresses and retired by counted lgkmcnt waits
+// (cdna_hip_programming.md §5.7 item 1 form (ii)), so hipcc neither serialises each fragment behind its own
+// wait nor drains the next block's LDS-DMA (vmcnt(0)) before them
+template <int OFF>
+__device__ __forceinline__ void ds_b128(u32x4& d, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
+}
+
 __device__ __forceinline__ float gelu_tanh(float x) {
   // 0.5 x (1 + tanh(u)) = x / (1 + exp(-2u)),  u = sqrt(2/pi) (x + 0.044715 x^3)
   // (nn.GELU(approximate='tanh')); 4 VALU + exp2 + rcp per element
